@@ -10,13 +10,25 @@ One "step" = one full training iteration of Runner.train (ray generation + rando
 network, compositing, Huber, backward, fused Adam+EMA; occupancy-grid refresh on every 16th step) over one 2^18-sample batch.
 
 Regime: a FIXED burn-in of --burn-in (1024) untimed steps brings the occupancy grid and the adaptive ray count to steady state regardless of --warmup; then
---warmup untimed steps, then exactly --steps timed steps between barrier + synchronize.  The last 32 burn-in steps run with an event pair around EVERY kernel
-launch of the library (csrc/prof.hip, on each launch's own stream) to find the kernel with the largest share of GPU time; in the timed region only that kernel
-keeps its bracket, and `roofline` is computed from those live durations.
+--warmup untimed steps, then exactly --steps timed steps between barrier + synchronize.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does that and nothing else: set-up, burn-in, warm-up, the N timed steps, the --dump-outputs files if asked
+for, the result line (`roofline` and `cpu_baseline` are null in it).  Everything else the benchmark measures is behind --full: the per-kernel event brackets and the
+`roofline` object (the last 32 burn-in steps run with an event pair around EVERY kernel launch of the library - csrc/prof.hip, on each launch's own stream - to find
+the kernel with the largest share of GPU time; in the timed region only that kernel keeps its bracket, and `roofline` is computed from those live durations), the test-view
+PSNR and render throughput, the CPU baseline, the `extra.spheres` / `extra.fox` / `extra.neus` / `extra.lego_gate` legs and, with --gpus > 1, the second timed region in
+the other scaling mode.  The --no-* options switch single parts of a --full run off.
+
+Set-up is dominated by the procedural scene (about two minutes of ray marching for the 100 x 800 x 800 views): SyntheticNerfDataset keeps a rendering that slow on disk
+(data/scene_cache, bit for bit the rendered tensor) and `bench.py --prepare`, run once by __graft_entry__.build() where a GPU is visible, puts it there.
+
+--dump-outputs DIR writes what the last timed step handed back and left behind - its per-ray loss and the parameters it updated - as DIR/<name>.npy (float32; arrays
+of more than 2^22 elements as a fixed, seeded sample of 2^22 of them).  The scene, the initial weights and the ray
+batches are seeded, so two runs with the same arguments train on identical inputs.
 
 `value` = (n_gpus * steps) / seconds (weak scaling: every rank trains its own 2^18-sample ray batch, hash-table / MLP gradients all-reduced over RCCL each step);
 --scaling strong splits ONE 2^18-sample iteration over the ranks (2^18 / n_gpus samples per rank), value = steps / seconds.
---config fox runs the ngp_fox.py hyper-parameters (aabb 4, cone stepping, fp16 fused MLP) instead; the default run reports that configuration on the REAL fox
+--config fox runs the ngp_fox.py hyper-parameters (aabb 4, cone stepping, fp16 fused MLP) instead; a --full run reports that configuration on the REAL fox
 images (data/fox, copied from the reference checkout by __graft_entry__.build()) under `extra.fox`.  Prints ONE JSON line on rank 0."""
 import argparse
 import json
@@ -302,6 +314,13 @@ def main():
     ap.add_argument("--burn-in", type=int, default=BURN_IN_DEFAULT, help="fixed number of untimed steps BEFORE --warmup (occupancy grid + adaptive ray count reach steady state)")
     ap.add_argument("--config", default="lego", choices=["lego", "fox"], help="lego = ngp_base.py hyper-parameters (headline); fox = ngp_fox.py hyper-parameters")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
+    ap.add_argument("--full", action="store_true", help="also measure everything that is not the headline figure: per-kernel event brackets + roofline, test-view PSNR and render "
+                    "throughput, CPU baseline, the spheres / real-fox / NeuS / lego-gate legs, --gpus > 1: the second timed region in the other scaling mode (the --no-* options below "
+                    "switch single parts of it off; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write the last timed step's per-ray loss and the parameters it left behind as DIR/<name>.npy "
+                    "(float32; large arrays as a fixed, seeded sample)")
+    ap.add_argument("--prepare", action="store_true", help="set up only: build the runner - which renders the procedural scene and keeps it on disk where rendering is slow "
+                    "(jnerf_amd/dataset.py) - and exit without a step or a result line; __graft_entry__.build() does this once, so that no run pays for the rendering")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-psnr", action="store_true")
     ap.add_argument("--no-fox", action="store_true", help="skip the real-fox leg (extra.fox)")
@@ -360,6 +379,8 @@ def main():
             target_batch_size=(1 << 18) // share, n_rays_per_batch=4096 // share, dp_force_collectives=bool(args.force_dist), dp_overlap=bool(args.dp_overlap), dp_host_sharded=bool(args.dp_host_sharded),
             **json.loads(os.environ.get("BENCH_EXTRA_CFG", "{}")))       # probe hook: extra config keys as JSON, e.g. {"pipeline_sampling": false}
     runner = Runner()
+    if args.prepare:
+        return
     import contextlib
     on_stream = contextlib.ExitStack()
     on_stream.enter_context(runner.training_stream())       # the loop of Runner.train runs on a stream of its own (runner.py); left (synchronised) after the timed region
@@ -370,7 +391,7 @@ def main():
         torch.cuda.synchronize()
 
     step = 0
-    probe = 0 if args.no_kernel_events else min(PROBE_STEPS, args.burn_in // 2)
+    probe = 0 if (args.no_kernel_events or not args.full) else min(PROBE_STEPS, args.burn_in // 2)
     for _ in range(args.burn_in - probe):
         runner.train_step(step); step += 1
     # ---- last `probe` burn-in steps: an event pair around EVERY kernel launch of the library (each on its own stream)
@@ -386,11 +407,11 @@ def main():
     probe_ms = ops.prof_read() if probe else {}
     # what an empty event pair measures on a stream (the two timestamp packets themselves): subtracted from every bracket
     pairs = []
-    for _ in range(64):
+    for _ in range(64 if probe else 0):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(); b.record(); pairs.append((a, b))
     torch.cuda.synchronize()
-    ev_overhead = sorted(a.elapsed_time(b) for a, b in pairs)[len(pairs) // 2]
+    ev_overhead = sorted(a.elapsed_time(b) for a, b in pairs)[len(pairs) // 2] if pairs else 0.0
     mean_valid = float(valid_sum.item()) / max(probe, 1) if probe else float(1 << 18) / share
     mean_rays = rays_sum / max(probe, 1) if probe else float(runner.sampler.n_rays_per_batch)
     per_step = {k: sum(max(x - ev_overhead, 0.0) for x in v) / probe for k, v in probe_ms.items()} if probe else {}
@@ -429,6 +450,8 @@ def main():
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, loss, write=rank == 0)
 
     # ---- roofline of the dominant kernel: live HIP-event durations over the timed region, algorithmic bytes per launch
     P = runner.model.pos_encoder.n_params
@@ -520,7 +543,7 @@ def main():
                 row["traffic"] = pmc[k]["hbm_bytes_per_launch"]
             pk[k] = row
         extra["probe_kernels"] = pk
-    if not args.no_psnr and rank == 0:
+    if args.full and not args.no_psnr and rank == 0:
         import numpy as np
         from jnerf_amd.utils.registry import build_from_cfg, DATASETS
         runner.dataset["test"] = build_from_cfg(runner.cfg.dataset.test, DATASETS)
@@ -552,7 +575,7 @@ def main():
                        "overlap": bool(args.dp_overlap), "n_ranks_seen": _dpm.n_ranks_seen() if in_lib else dist.get_world_size(),
                        "dp_exchange": getattr(getattr(runner, "_fast", None), "dp_exchange", None), "grad_wire": "fp16 x 2^14" if getattr(getattr(runner, "_fast", None), "_grad_wire", None) is not None else "fp32",
                        "scaling_curve": "this line is ONE point; no multi-GPU scaling curve has been measured by the authors (one-GPU boxes only)"}
-    if use_dist and world > 1 and not args.no_second_scaling:
+    if args.full and use_dist and world > 1 and not args.no_second_scaling:
         # (r6) SURVEY.md 8(e) makes STRONG scaling (one 2^18-sample iteration split over the ranks: the same optimisation trajectory at every N) the primary
         # multi-GPU figure, the driver's contract line is weak scaling: one run prints both.  A second, shorter timed region in the other mode, on every rank (collective);
         # `value` above is untouched by it.
@@ -587,18 +610,18 @@ def main():
         except Exception as e:        # (deterministic failures hit every rank alike; the contract line must survive them)
             extra["dp"]["other_scaling"] = {"scaling": other, "error": repr(e)[:300]}
         runner = None
-    if rank == 0 and not use_dist and lego and scene != "spheres" and not args.no_spheres:
+    if args.full and rank == 0 and not use_dist and lego and scene != "spheres" and not args.no_spheres:
         del runner
         runner = None
         torch.cuda.empty_cache()
         extra["spheres"] = spheres_leg(n_images, res)
-    if rank == 0 and not use_dist and not args.no_fox:
+    if args.full and rank == 0 and not use_dist and not args.no_fox:
         runner = None
         torch.cuda.empty_cache()
         extra["fox"] = fox_leg()
-    if rank == 0 and not use_dist and not args.no_neus:
+    if args.full and rank == 0 and not use_dist and not args.no_neus:
         extra["neus"] = neus_leg()
-    if rank == 0 and not use_dist and not args.no_lego_gate:
+    if args.full and rank == 0 and not use_dist and not args.no_lego_gate:
         # the headline gate itself (README.md:114-120): runs when NeRF-synthetic lego is mounted ($NGP_LEGO_DIR | data/lego), says "not runnable" otherwise (tools/lego_gate.py)
         runner = None
         torch.cuda.empty_cache()
@@ -622,12 +645,35 @@ def main():
                                        f", random-init weights, {args.burn_in}-step burn-in before warm-up", "scene": scene,
                            "samples_per_iter_per_gpu": (1 << 18) // share, "parallelism": f"ray-batch dp{world} ({args.scaling} scaling)" if world > 1 else "single",
                            **({"dp_exchange": dp_exchange_used} if use_dist else {})},
-                "roofline": roof, "cpu_baseline": None if (args.no_cpu_baseline or use_dist) else cpu_baseline(aabb_scale, fp16, const_dt), "extra": extra}
+                "roofline": roof, "cpu_baseline": cpu_baseline(aabb_scale, fp16, const_dt) if (args.full and not args.no_cpu_baseline and not use_dist) else None, "extra": extra}
         print(json.dumps(line), flush=True)
     if use_dist:
         from jnerf_amd import dp as _dp
         _dp.destroy()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 22          # elements kept of a larger array (16 MB as float32)
+
+
+def dump_outputs(path, runner, loss, write=True):
+    """--dump-outputs: the arrays the last timed step handed back (its per-ray Huber loss, [rays, 3]) and left behind (every parameter of the model after its sweep) as
+    <path>/<name>.npy in float32.  An array of more than DUMP_SAMPLE elements is written flat, as its elements at fixed positions (sorted draw of
+    numpy.random.default_rng(0) over the array's size), so the files of one run stay far below 64 MB and two builds can be compared element for element."""
+    import numpy as np
+    from jnerf_amd import optim
+    optim.flush_all(); optim.sync_all_sharded()           # (data parallel, every rank: deferred sweeps and moments kept on their owner's shard are completed before parameters are read)
+    if not write:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = {} if loss is None else {"loss": loss}
+    for name, p in runner.model.named_parameters():
+        arrays["param." + name] = p
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().reshape(-1) if t.numel() > DUMP_SAMPLE else t.detach().float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def neus_leg(warm=100, timed=200):

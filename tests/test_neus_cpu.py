@@ -8,8 +8,8 @@ import torch
 
 from jnerf_amd.utils.config import Config, get_cfg, reset_cfg
 from tests import synth_dtu
+from tests.reference_configs import reference_dump
 
-REF = "/root/reference/projects/neus/configs"
 HERE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "projects", "neus", "configs")
 
 
@@ -31,10 +31,9 @@ def tiny_cfg(root, **over):
     return reset_cfg(**cfg)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
 @pytest.mark.parametrize("name", ["neus_womask.py", "neus_wmask.py"])
 def test_neus_configs_equal_the_references(name):
-    ours, ref = Config(os.path.join(HERE, name)).dump(), Config(os.path.join(REF, name)).dump()
+    ours, ref = Config(os.path.join(HERE, name)).dump(), reference_dump("neus/configs/" + name)         # (the reference's file as recorded by tests/golden/make_golden_configs.py)
     for d in (ours, ref):
         for k in ("name", "work_dir"):
             d.pop(k, None)

@@ -143,7 +143,7 @@ def test_two_ranks_data_parallel_on_one_gpu(scaling):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "20", "--warmup", "8", "--burn-in", "32", "--config", "fox", "--images", "4", "--res", "64", "--no-psnr", "--scaling", scaling]
+           os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "20", "--warmup", "8", "--burn-in", "32", "--config", "fox", "--images", "4", "--res", "64", "--no-psnr", "--scaling", scaling]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -305,7 +305,7 @@ def test_rccl_fp16_gradient_wire_in_the_fp32_configuration():
 
 def test_bench_contract_small():
     """the bench line's contract on a tiny workload: metric / value / roofline (dominant kernel chosen over ALL kernels, live durations) / per-kernel table"""
-    d = _run_bench(["--steps", "16", "--warmup", "4", "--burn-in", "64", "--images", "8", "--res", "96", "--no-fox", "--no-cpu-baseline"])
+    d = _run_bench(["--full", "--steps", "16", "--warmup", "4", "--burn-in", "64", "--images", "8", "--res", "96", "--no-fox", "--no-cpu-baseline"])
     assert d["metric"] == "training iters/s" and d["dtype"] == "f32" and d["scaling"] == "weak" and d["n_gpus"] == 1 and d["value"] > 0
     rf = d["roofline"]
     assert rf["bound"] in ("hbm", "mfma") and rf["kernel"] in rf["ms_per_step_by_kernel"] and rf["launches_timed"] >= 8
@@ -323,6 +323,33 @@ def test_bench_contract_small():
     for k, row in d["extra"]["probe_kernels"].items():
         assert (row["frac_hbm"] is None and row.get("served_from_cache") and row["avg_launch_ms"] < 0.02) or row["frac_hbm"] <= 1.0, (k, row)      # (only a few-microsecond kernel on cache-resident data may exceed HBM's rate; it then carries no fraction)
         assert row.get("frac_mfma", 0.0) <= 1.0, (k, row)
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """a run without --full is the headline figure and nothing else (no kernel brackets / roofline, no PSNR or render timing, no CPU baseline, no extra leg); --steps is the
+    number of timed steps and ms_per_step their mean; --dump-outputs writes the last timed step's per-ray loss and the parameters it left behind as float32 .npy files
+    (large arrays as a fixed sample: 64 MB at most in all), and a second run with the same arguments - same seeded scene, weights and ray batches - writes the same arrays
+    (fp32 configuration, one process: runs are reproducible to the bit, as test_rccl_exchange_step_adds_no_arithmetic relies on too)"""
+    import os
+    common = ["--gpus", "1", "--steps", "12", "--warmup", "4", "--burn-in", "64", "--images", "8", "--res", "96"]
+    runs = [_run_bench(common + ["--dump-outputs", str(tmp_path / tag)]) for tag in ("a", "b")]
+    for d in runs:
+        assert d["metric"] == "training iters/s" and d["unit"] == "iters/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["n_gpus"] == 1
+        assert d["steps"] == 12 and d["warmup"] == 4 and d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) <= 10.0       # value = steps / seconds, ms_per_step = seconds / steps
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["extra"]["probe_steps"] == 0
+        assert not ({"probe_kernels", "spheres", "fox", "neus", "lego_gate"} & set(d["extra"])) and not any(k.startswith(("psnr", "render_")) for k in d["extra"])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "loss.npy" in names and any(n.startswith("param.") for n in names) and all(n.endswith(".npy") for n in names)
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and x.size > 0 and np.isfinite(x).all(), n
+        assert np.array_equal(x, y), (n, float(np.abs(x - y).max()) if x.shape == y.shape else (x.shape, y.shape))
+        total += os.path.getsize(tmp_path / "a" / n)
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.ndim == 2 and loss.shape[1] == 3 and abs(float(loss.mean()) - runs[0]["loss"]) <= 1e-5 + 1e-4 * abs(runs[0]["loss"])     # the array behind the line's `loss`
+    assert total <= 64 << 20
+    assert max(np.load(tmp_path / "a" / n).size for n in names) <= 1 << 22                      # the hash table (12.2 M parameters) went out as its fixed sample
 
 
 def test_render_survives_sample_capacity_overflow():

@@ -18,16 +18,16 @@ diff /tmp/bits_prev.txt /tmp/bits_new.txt && echo "all bits identical"
 for i in $(seq 1 $lreps); do
   for v in prev new; do
     cp /tmp/lib_$v.so $R/jnerf_amd/csrc/libngp_hip.so
-    (cd $R && timeout 600 python bench.py --no-fox --no-neus --no-cpu-baseline --no-psnr --no-spheres --no-lego-gate --steps 200 --config lego > gpurun_out/ab.json 2> gpurun_out/ab.err)
+    (cd $R && timeout 600 python bench.py --full --no-fox --no-neus --no-cpu-baseline --no-psnr --no-spheres --no-lego-gate --steps 200 --config lego > /tmp/ab.json 2> /tmp/ab.err)
     python - <<PY
 import json
 try:
-    d = json.loads([l for l in open('$R/gpurun_out/ab.json') if l.startswith('{"metric')][-1])
+    d = json.loads([l for l in open('/tmp/ab.json') if l.startswith('{"metric')][-1])
     k = d['roofline']['ms_per_step_by_kernel']
     print('lego', '[$v]', d['value'], d['ms_per_step'], {x: k[x] for x in list(k)[:9]}, 'render', d.get('extra', {}).get('render_Msamples_per_s'), flush=True)
     open('/tmp/ab_lego_$v.txt', 'a').write('%f\n' % d['value'])
 except Exception as e:
-    print('lego [$v] failed', e, open('$R/gpurun_out/ab.err').read()[-400:], flush=True)
+    print('lego [$v] failed', e, open('/tmp/ab.err').read()[-400:], flush=True)
 PY
   done
 done

@@ -10,15 +10,15 @@ cp $R/jnerf_amd/csrc/libngp_hip.so /tmp/lib_new.so
 for i in $(seq 1 $reps); do
   for v in prev new; do
     cp /tmp/lib_$v.so $R/jnerf_amd/csrc/libngp_hip.so
-    (cd $R && timeout 600 python bench.py --no-fox --no-neus --no-cpu-baseline --no-spheres --no-lego-gate --steps 100 > gpurun_out/ab.json 2> gpurun_out/ab.err)
+    (cd $R && timeout 600 python bench.py --full --no-fox --no-neus --no-cpu-baseline --no-spheres --no-lego-gate --steps 100 > /tmp/ab.json 2> /tmp/ab.err)
     python - <<PY
 import json
 try:
-    d = json.loads([l for l in open('$R/gpurun_out/ab.json') if l.startswith('{"metric')][-1])
+    d = json.loads([l for l in open('/tmp/ab.json') if l.startswith('{"metric')][-1])
     e = d['extra']
     print('render [$v]', d['value'], 'it/s;', e.get('render_Msamples_per_s'), 'Msamples/s', {k: v for k, v in e.items() if k.startswith('render_ms') or k.startswith('psnr')}, flush=True)
 except Exception as ex:
-    print('render [$v] failed', ex, open('$R/gpurun_out/ab.err').read()[-400:], flush=True)
+    print('render [$v] failed', ex, open('/tmp/ab.err').read()[-400:], flush=True)
 PY
   done
 done

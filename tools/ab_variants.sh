@@ -19,15 +19,15 @@ for i in $(seq 1 $reps); do
     envs="A=$i"; lib=/tmp/lib_base.so
     if [ "${flags:0:1}" = "@" ]; then envs="${flags:1}"; elif [ -n "$flags" ]; then lib=/tmp/lib_$name.so; fi
     cp $lib $R/jnerf_amd/csrc/libngp_hip.so
-    (cd $R && env $envs timeout 600 python bench.py --no-fox --no-neus --no-cpu-baseline --no-psnr --no-spheres --no-lego-gate --steps 200 --config $cfg > gpurun_out/ab.json 2> gpurun_out/ab.err)
+    (cd $R && env $envs timeout 600 python bench.py --full --no-fox --no-neus --no-cpu-baseline --no-psnr --no-spheres --no-lego-gate --steps 200 --config $cfg > /tmp/ab.json 2> /tmp/ab.err)
     python - <<PY
 import json
 try:
-    d = json.loads([l for l in open('$R/gpurun_out/ab.json') if l.startswith('{"metric')][-1])
+    d = json.loads([l for l in open('/tmp/ab.json') if l.startswith('{"metric')][-1])
     k = d['roofline']['ms_per_step_by_kernel']
     print('$cfg', '[$name]', d['value'], d['ms_per_step'], {x: k[x] for x in list(k)[:9]}, flush=True)
 except Exception as e:
-    print('$cfg [$name] failed', e, open('$R/gpurun_out/ab.err').read()[-400:], flush=True)
+    print('$cfg [$name] failed', e, open('/tmp/ab.err').read()[-400:], flush=True)
 PY
   done
 done

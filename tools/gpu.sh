@@ -14,15 +14,15 @@ tests)
 ab)
   cfg=$1; shift
   for variant in "A=1" "$@"; do
-    env $variant timeout 600 python bench.py --no-fox --no-neus --no-cpu-baseline --no-psnr --steps 200 --config $cfg > gpurun_out/ab.json 2> gpurun_out/ab.err
+    env $variant timeout 600 python bench.py --full --no-fox --no-neus --no-cpu-baseline --no-psnr --steps 200 --config $cfg > /tmp/ab.json 2> /tmp/ab.err
     python - <<PY
 import json
 try:
-    d = json.loads([l for l in open('gpurun_out/ab.json') if l.startswith('{"metric')][-1])
+    d = json.loads([l for l in open('/tmp/ab.json') if l.startswith('{"metric')][-1])
     k = d['roofline']['ms_per_step_by_kernel']
     print('$cfg', '[$variant]', d['value'], d['ms_per_step'], {x: k[x] for x in list(k)[:8]}, flush=True)
 except Exception as e:
-    print('$cfg [$variant] failed', e, open('gpurun_out/ab.err').read()[-600:], flush=True)
+    print('$cfg [$variant] failed', e, open('/tmp/ab.err').read()[-600:], flush=True)
 PY
   done 2>&1 | tee -a gpurun_out/ab_lines.txt
   ;;

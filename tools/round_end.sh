@@ -9,8 +9,8 @@ if [ $WHAT = all ] || [ $WHAT = tests ]; then
 bash tools/gpu.sh tests > /dev/null 2>&1; tail -6 gpurun_out/tests_gpu.log; cp gpurun_out/tests_gpu.log gpurun_out/${TAG}_tests_gpu.log
 fi
 if [ $WHAT = all ] || [ $WHAT = bench ]; then
-bash tools/gpu.sh bench ${TAG}_bench_lego
-bash tools/gpu.sh bench ${TAG}_bench_fox --config fox --no-fox --no-neus
+bash tools/gpu.sh bench ${TAG}_bench_lego --full
+bash tools/gpu.sh bench ${TAG}_bench_fox --full --config fox --no-fox --no-neus
 bash tools/gpu.sh bench ${TAG}_bench_driver_style --gpus 1 --steps 20 --warmup 5
 fi
 if [ $WHAT = all ] || [ $WHAT = profiles ]; then
