@@ -902,13 +902,36 @@ __host__ __device__ __forceinline__ uint32_t bin2_of(uint32_t e, bool il) { retu
 __host__ __device__ __forceinline__ uint32_t local2_of(uint32_t e, bool il) { return il ? ((e >> 10) << 3) | (e & 7u) : e & (PAIR_BIN_ENTRIES - 1u); }
 __host__ __device__ __forceinline__ uint32_t entry2_of(uint32_t bin, uint32_t local, bool il) { return il ? ((local >> 3) << 10) | (bin << 3) | (local & 7u) : (bin << PAIR_BIN_BITS) | local; }
 
-template <typename T, int LAYOUT, int OCC>
+// (r7) timing build -DNGP_PROBE_CLOCK (tools/probe_hash_bwd_phases.py): thread 0 of every workgroup of k_bin_runs2 (K = 0) and k_bin_accumulate2 (K = 1) stamps the 100 MHz
+// wall clock at its phase boundaries; results are unchanged, the build is never the product
+#ifdef NGP_PROBE_CLOCK
+#define PROBE_CLOCK_WGS 4096u
+#define PROBE_CLOCK_SLOTS 8u
+__device__ unsigned long long g_probe_clock[2][PROBE_CLOCK_WGS][PROBE_CLOCK_SLOTS];
+#define PROBE_TICK(K, WG, I) do { if (threadIdx.x == 0 && (WG) < PROBE_CLOCK_WGS) g_probe_clock[K][WG][I] = wall_clock64(); } while (0)
+NGP_API int ngp_x_probe_clock(unsigned long long *out_host, int clear) {
+	hipError_t e = hipDeviceSynchronize();
+	if (e == hipSuccess && out_host) e = hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_probe_clock), sizeof(g_probe_clock));
+	if (e == hipSuccess && clear) { void *d = nullptr; e = hipGetSymbolAddress(&d, HIP_SYMBOL(g_probe_clock)); if (e == hipSuccess) e = hipMemset(d, 0, sizeof(g_probe_clock)); }
+	return (int)e;
+}
+#else
+#define PROBE_TICK(K, WG, I) do {} while (0)
+#endif
+
+// (r7, profiles/r07_hash_bwd_stage.md) V2: (a) all 1280 workgroups start together and every one of them began with its unit of the MLP tail - two dependent rounds of loads,
+// 6.4 us in which the whole GPU waited; now the odd workgroups carry their unit at their END, so one half's latency lies under the other half's sweeps.  (b) the thread keeps
+// p = pos * scale + 0.5 (24 registers) and takes cell and fraction from it in each sweep instead of keeping both (48): nothing spills at five waves per SIMD.  Same records.
+template <typename T, int LAYOUT, int OCC, bool V2 = false>
 __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const float *__restrict__ pos, uint32_t stride, const T *__restrict__ dLdy, LevelTable lt, BinPlan bp, LevelSel sel,
                                                          const uint32_t *__restrict__ absmax_bits, RunRec *__restrict__ rrec, uint16_t *__restrict__ roff,
                                                          const uint32_t *__restrict__ n_valid, uint32_t stage /* records of LDS staging */, TailJobs tj) {
 	extern __shared__ __attribute__((aligned(16))) uint32_t bin_smem[];
 	const uint32_t ro = blockIdx.y;
-	if (tj.do_reduce) tail_reduce_share(tj, reinterpret_cast<float *>(bin_smem), ro * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);      // (r6, mlp_tail.h) this workgroup's 8 columns of the MLP weight-gradient slabs (+ their parameters' sweep)
+	PROBE_TICK(0, ro * gridDim.x + blockIdx.x, 0);
+	const bool tail_last = V2 && tj.do_reduce && ((ro * gridDim.x + blockIdx.x) & 1u);
+	if (tj.do_reduce && !tail_last) tail_reduce_share(tj, reinterpret_cast<float *>(bin_smem), ro * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);      // (r6, mlp_tail.h) this workgroup's 8 columns of the MLP weight-gradient slabs (+ their parameters' sweep)
+	PROBE_TICK(0, ro * gridDim.x + blockIdx.x, 1);
 	RunRec *stage_rec = reinterpret_cast<RunRec *>(bin_smem);                              // [stage]
 	uint32_t *cnt = bin_smem + stage * 3u, *loff = cnt + PAIR_BINS, *cnt2 = loff + PAIR_BINS + 2u;   // loff[PAIR_BINS] = total
 	const uint32_t hl = sel.hl[ro], level = bp.level[hl];
@@ -920,6 +943,7 @@ __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const flo
 	uint32_t lim = n; if (n_valid) { uint32_t nv = *n_valid; lim = nv < n ? nv : n; }
 	if (level_absmax(absmax_bits, level) == 0u || blockIdx.x * RUN_WG * RUN_K >= lim) {        // uniform exit: an empty region
 		if (threadIdx.x < RUN2_OFFS) my_off[threadIdx.x] = 0;
+		if (tail_last) tail_reduce_share(tj, reinterpret_cast<float *>(bin_smem), ro * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
 		return;
 	}
 	if (threadIdx.x < PAIR_BINS) { cnt[threadIdx.x] = 0; cnt2[threadIdx.x] = 0; }
@@ -927,7 +951,7 @@ __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const flo
 	const uint32_t first = (blockIdx.x * RUN_WG + threadIdx.x) * RUN_K;
 	using P = typename Pair<T>::type;
 	const P *dy = reinterpret_cast<const P *>(dLdy);
-	uint32_t cell[RUN_K][3]; float frac[RUN_K][3]; float2 gk[RUN_K];
+	uint32_t cell[V2 ? 1 : RUN_K][3]; float frac[V2 ? 1 : RUN_K][3]; float pp[V2 ? RUN_K : 1][3]; float2 gk[RUN_K];   // V2: pp = pos * scale + 0.5; cell and fraction are taken from it in the sweeps
 	{
 		float px[RUN_K][3];
 		if (first + RUN_K <= lim && stride == 3) {
@@ -962,8 +986,12 @@ __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const flo
 #pragma unroll
 		for (uint32_t k = 0; k < RUN_K; ++k)
 #pragma unroll
-			for (int d = 0; d < 3; ++d) { const float p = px[k][d] * scale + 0.5f; const float fl = floorf(p); cell[k][d] = (uint32_t)(int)fl; frac[k][d] = p - fl; }   // pos_fract, HashEncode.h:106-115
+			for (int d = 0; d < 3; ++d) {                                                  // pos_fract, HashEncode.h:106-115
+				const float p = px[k][d] * scale + 0.5f;
+				if constexpr (V2) pp[k][d] = p; else { const float fl = floorf(p); cell[k][d] = (uint32_t)(int)fl; frac[k][d] = p - fl; }
+			}
 	}
+	PROBE_TICK(0, (uint32_t)region, 2);
 	// one sweep over the thread's samples; emit(entry, x, y) is called for the eight corners of every finished run (k_bin_records_runs' sweep)
 	auto sweep = [&](auto emit) {
 		bool open = false;
@@ -978,13 +1006,19 @@ __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const flo
 #pragma unroll
 		for (uint32_t k = 0; k < RUN_K; ++k) {
 			if (gk[k].x == 0.f && gk[k].y == 0.f) continue;        // zero rows (padding) add exact zeros in the reference: skipped, they do not end a run either
-			if (open && !(cell[k][0] == key[0] && cell[k][1] == key[1] && cell[k][2] == key[2])) { flush(); open = false; }
+			uint32_t ck[3]; float fk[3];
+#pragma unroll
+			for (int d = 0; d < 3; ++d) {
+				if constexpr (V2) { const float fl = floorf(pp[k][d]); ck[d] = (uint32_t)(int)fl; fk[d] = pp[k][d] - fl; }
+				else { ck[d] = cell[k][d]; fk[d] = frac[k][d]; }
+			}
+			if (open && !(ck[0] == key[0] && ck[1] == key[1] && ck[2] == key[2])) { flush(); open = false; }
 			if (!open) {
-				open = true; key[0] = cell[k][0]; key[1] = cell[k][1]; key[2] = cell[k][2];
+				open = true; key[0] = ck[0]; key[1] = ck[1]; key[2] = ck[2];
 #pragma unroll
 				for (uint32_t q = 0; q < 8; ++q) { ax[q] = 0.f; ay[q] = 0.f; }
 			}
-			const float x1 = frac[k][0], x0 = 1 - x1, y1 = frac[k][1], y0 = 1 - y1, z1 = frac[k][2], z0 = 1 - z1;
+			const float x1 = fk[0], x0 = 1 - x1, y1 = fk[1], y0 = 1 - y1, z1 = fk[2], z0 = 1 - z1;
 #pragma unroll
 			for (uint32_t q = 0; q < 8; ++q) {
 				const float w = ((q & 1u) ? x1 : x0) * ((q & 2u) ? y1 : y0) * ((q & 4u) ? z1 : z0);                 // the reference's x, y, z multiplication order
@@ -995,6 +1029,13 @@ __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const flo
 	};
 	sweep([&](uint32_t e, float, float) { atomicAdd(&cnt[bin2_of(e, il)], 1u); });
 	__syncthreads();
+	PROBE_TICK(0, (uint32_t)region, 3);
+	if constexpr (V2) {                                                         // the second sweep takes cell and fraction from pp AGAIN: values of the first kept alive across the passes are what spilled
+#pragma unroll
+		for (uint32_t k = 0; k < RUN_K; ++k)
+#pragma unroll
+			for (int d = 0; d < 3; ++d) asm volatile("" : "+v"(pp[k][d]));
+	}
 	if (threadIdx.x < 64u) {                                                    // wave 0, two bins per lane: exclusive prefix = the region's bin offsets
 		const uint32_t b0 = 2u * threadIdx.x, c0 = cnt[b0], c1 = cnt[b0 + 1u];
 		uint32_t x = c0 + c1;
@@ -1006,6 +1047,7 @@ __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const flo
 		if (threadIdx.x == 63u) { loff[PAIR_BINS] = x; reinterpret_cast<uint32_t *>(my_off)[64] = x; }
 	}
 	__syncthreads();
+	PROBE_TICK(0, (uint32_t)region, 4);
 	RunRec *out = rrec + region * run2_region_records();
 	sweep([&](uint32_t e, float x, float y) {
 		const uint32_t bin = bin2_of(e, il), p = loff[bin] + atomicAdd(&cnt2[bin], 1u);
@@ -1013,11 +1055,18 @@ __global__ __launch_bounds__(RUN_WG, OCC) void k_bin_runs2(uint32_t n, const flo
 		if (p < stage) stage_rec[p] = r; else out[p] = r;                      // beyond the staging area (scattered positions only): straight to its place in the region
 	});
 	__syncthreads();
+	PROBE_TICK(0, (uint32_t)region, 5);
 	const uint32_t total = min(loff[PAIR_BINS], stage);
 #ifdef NGP_PROBE_SCATTER                                                                  // timing experiment: no record stores from the staging area - results WRONG
 	if (total != 0x7fffffffu) return;
 #endif
 	for (uint32_t p = threadIdx.x; p < total; p += RUN_WG) out[p] = stage_rec[p];
+	PROBE_TICK(0, (uint32_t)region, 6);
+	if (tail_last) {                                                            // (the staging area is the unit's scratch: every thread has copied its records out)
+		__syncthreads();
+		tail_reduce_share(tj, reinterpret_cast<float *>(bin_smem), ro * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+		PROBE_TICK(0, (uint32_t)region, 7);
+	}
 }
 
 // ---- ONE accumulate kernel for every level of the fp32 path: a workgroup per (level, 4096-entry bin), 64 KiB of 64-bit accumulators (two workgroups per CU).  It walks
@@ -1150,6 +1199,7 @@ __global__ __launch_bounds__(ACC2_WG, 4) void k_bin_accumulate2(LevelTable lt, B
 	const uint32_t n_units = (ap.n_pair + ap.n_run) * PAIR_BINS;
 	const uint32_t u_this = blockIdx.x;
 	if (u_this >= n_units) return;
+	PROBE_TICK(1, blockIdx.x, 0);
 	{
 		const bool pr0 = u_this < ap.n_pair * PAIR_BINS;
 		const uint32_t v0 = pr0 ? u_this : u_this - ap.n_pair * PAIR_BINS;
@@ -1192,6 +1242,7 @@ __global__ __launch_bounds__(ACC2_WG, 4) void k_bin_accumulate2(LevelTable lt, B
 	}
 	for (uint32_t e = threadIdx.x; e < n_local; e += ACC2_WG) { iacc[2 * e] = 0ull; iacc[2 * e + 1] = 0ull; }
 	__syncthreads();
+	PROBE_TICK(1, blockIdx.x, 1);
 #ifdef NGP_PROBE_ACC_U32_CARRY
 	// diagnosis build (tools/probe_acc_carry.sh): the 64-bit sum as two 32-bit LDS atomics with carry instead of ds_add_u64 - the low word's returning add
 	// tells the one thread whose add wrapped it, which adds the carry to the high word; adds commute, so the final sum is the same integer.  Same results, slower; never the product.
@@ -1236,7 +1287,9 @@ __global__ __launch_bounds__(ACC2_WG, 4) void k_bin_accumulate2(LevelTable lt, B
 		for (uint32_t k = 0; k < 4u; ++k) { const uint32_t q = threadIdx.x + k * ACC2_WG; rp[k] = Pq[q]; rm[k] = MV_LD(Mq + q); rv[k] = MV_LD(Vq + q); }
 	}
 #endif
+	PROBE_TICK(1, blockIdx.x, 2);
 	__syncthreads();
+	PROBE_TICK(1, blockIdx.x, 3);
 	if (ADAM) {                                                           // the sweep instead of the gradient store: same entries per thread as below; all of a thread's loads first
 		static_assert(PAIR_BIN_ENTRIES == 8u * ACC2_WG, "eight entries per thread");
 		if (!il) {
@@ -1298,6 +1351,7 @@ __global__ __launch_bounds__(ACC2_WG, 4) void k_bin_accumulate2(LevelTable lt, B
 			dst[t] = o;
 		}
 	}
+	PROBE_TICK(1, blockIdx.x, 4);
 	}
 }
 // the accumulate with the table's sweep riding, under its own name for NGP_LAUNCH's brackets (bench.py tells the two apart; rocprof shows the template arguments)
@@ -1414,6 +1468,7 @@ static int hash_bwd_set_lds() {
 	SET((k_bin_pairs<float, NGP_LAYOUT_SOA, 512u>), pair_stage_bytes()); SET((k_bin_pairs<float, NGP_LAYOUT_AOS, 512u>), pair_stage_bytes());
 	SET((k_bin_pairs<float, NGP_LAYOUT_SOA, 1024u>), pair_stage_bytes()); SET((k_bin_pairs<float, NGP_LAYOUT_AOS, 1024u>), pair_stage_bytes());
 	SET((k_bin_runs2<float, NGP_LAYOUT_SOA, 5>), run2_stage_bytes(RUN2_STAGE)); SET((k_bin_runs2<float, NGP_LAYOUT_AOS, 5>), run2_stage_bytes(RUN2_STAGE));
+	SET((k_bin_runs2<float, NGP_LAYOUT_SOA, 5, true>), run2_stage_bytes(RUN2_STAGE)); SET((k_bin_runs2<float, NGP_LAYOUT_AOS, 5, true>), run2_stage_bytes(RUN2_STAGE));
 #undef SET_T
 	SET((k_bin_accumulate2<float, false>), PAIR_BIN_ENTRIES * 16u + ACC2_LDS_EXTRA);
 	SET((k_bin_accumulate2<float, true>), PAIR_BIN_ENTRIES * 16u + ACC2_LDS_EXTRA);
@@ -1516,11 +1571,15 @@ static int hash_bwd_impl(void *stream, uint32_t n, const float *pos, uint32_t po
 		// (r6) the MLP tail rides along when both record kernels run: every workgroup of k_bin_runs2 reduces its share of the slabs and sweeps those parameters, every workgroup
 		// of k_bin_pairs - the next launch in the stream, so it reads the swept pack - gathers its share of the fragment buffer (mlp_tail.h)
 		TailJobs tj_run = no_tail_jobs(), tj_pair = no_tail_jobs();
-		if (tail && tail->do_reduce && tail->do_sweep && tail->pack_table && n_runs && n_pair && n > 0) {
+		if (tail && tail->do_reduce && tail->do_sweep && tail->pack_table && n_runs && n_pair && n > 0 && (uint64_t)tail->n_slabs * tail->width < (1ull << 32)) {   // (the rider indexes the slabs with 32 bits)
 			tj_run = *tail; tj_pair = *tail; tj_pair.do_reduce = 0;
 			if (tail_taken) *tail_taken = 1;
 		}
-#define RGO(L) NGP_LAUNCH((k_bin_runs2<float, L, 5>), dim3(div_up(n, RUN_WG * RUN_K), n_runs), dim3(RUN_WG), run2_stage_bytes(RUN2_STAGE), s, n, pos, pos_stride, (const float *)dLdy, lt, bp, sel_runs, (const uint32_t *)absmax, run_rec, run_off, n_valid, RUN2_STAGE, tj_run)
+		// A/B hook NGP_HASH_BWD_RUNS: 1 (default) = k_bin_runs2's V2 form (r7: half the workgroups carry their tail unit last, nothing spills), 0 = round 4-6's; same records, same brackets
+		const char *runs_env = getenv("NGP_HASH_BWD_RUNS");                   // (read per call: tests/test_hash_bwd_stage.py compares the two forms in one process)
+		const int runs_v2 = runs_env ? atoi(runs_env) : 1;
+#define RGO_(L, V2) NGP_LAUNCH((k_bin_runs2<float, L, 5, V2>), dim3(div_up(n, RUN_WG * RUN_K), n_runs), dim3(RUN_WG), run2_stage_bytes(RUN2_STAGE), s, n, pos, pos_stride, (const float *)dLdy, lt, bp, sel_runs, (const uint32_t *)absmax, run_rec, run_off, n_valid, RUN2_STAGE, tj_run)
+#define RGO(L) do { if (runs_v2) RGO_(L, true); else RGO_(L, false); } while (0)
 // (k_bin_pairs depends on the abs-max pass like k_bin_runs2 does, not on k_bin_runs2: both are plain in-order launches - the any-order launch of round 4 lost its A/B and raced with the abs-max pass when there was no run level)
 #define PGO(L, S) NGP_LAUNCH((k_bin_pairs<float, L, S>), dim3(div_up(n, S), n_pair), dim3(S), pair_stage_bytes(), s, n, pos, pos_stride, (const float *)dLdy, lt, bp, sel_pair, (const uint32_t *)absmax, pair_rec, pair_off, spill_count, spill, n_valid, tj_pair)
 #define RECORDS(L) do { ABSMAX(float, L); if (n_runs) RGO(L); if (n_pair) { if (pair_s == 512u) PGO(L, 512u); else PGO(L, 1024u); } } while (0)
@@ -1528,6 +1587,7 @@ static int hash_bwd_impl(void *stream, uint32_t n, const float *pos, uint32_t po
 #undef RECORDS
 #undef PGO
 #undef RGO
+#undef RGO_
 		auto accumulate = [&](bool runs, bool pairs) {
 			Acc2Plan ap;
 			ap.n_pair = pairs ? n_pair : 0u; ap.n_run = runs ? n_runs : 0u;
@@ -1553,7 +1613,7 @@ static int hash_bwd_impl(void *stream, uint32_t n, const float *pos, uint32_t po
 		uint16_t *rec_idx = (uint16_t *)(ws + wl.rec_idx);
 		// (r6) fp16 configuration: the slab reduction that also sweeps the two MLP packs (k_reduce_slabs_sweep's job) rides as row 0 of the run-record launch
 		TailJobs tj_pc = no_tail_jobs();
-		if (tail && tail->do_reduce && tail->do_sweep16 && !tail->do_sweep && n_runs && n > 0) { tj_pc = *tail; if (tail_taken) *tail_taken = 1; }
+		if (tail && tail->do_reduce && tail->do_sweep16 && !tail->do_sweep && n_runs && n > 0 && (uint64_t)tail->n_slabs * tail->width < (1ull << 32)) { tj_pc = *tail; if (tail_taken) *tail_taken = 1; }
 #define GO(T, G, L) do { \
 	using RV_ = typename RecVal<T>::type; \
 	ABSMAX(T, L); \

@@ -73,7 +73,7 @@ __device__ __forceinline__ void tail_reduce_cols8(const TailJobs &tj, float *lds
 			for (uint32_t k0 = q; k0 < tj.n_slabs; k0 += 256u) {          // sixteen loads in flight, added in slab order
 				float v[16];
 #pragma unroll
-				for (uint32_t j = 0; j < 16; ++j) { const uint32_t k = k0 + 16u * j; v[j] = k < tj.n_slabs ? tj.slabs[(size_t)k * tj.width + col] : 0.f; }
+				for (uint32_t j = 0; j < 16; ++j) { const uint32_t k = k0 + 16u * j; v[j] = k < tj.n_slabs ? tj.slabs[k * tj.width + col] : 0.f; }      // (32-bit element index: one offset register per load in flight; the slabs are far below 2^32 floats)
 #pragma unroll
 				for (uint32_t j = 0; j < 16; ++j) if (k0 + 16u * j < tj.n_slabs) s += v[j];
 			}
