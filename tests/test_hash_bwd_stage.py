@@ -1,6 +1,8 @@
-"""(r7) The hash-backward stage of the fp32 step: k_bin_runs2 (run records) + k_bin_pairs + k_bin_accumulate2.
+"""(r7) The hash-backward stage: k_bin_runs2 (run records) + k_bin_pairs + k_bin_accumulate2 of the fp32 step (csrc/hash_bwd_regions.h), k_bin_records_runs + k_bin_records +
+k_bin_accumulate of the fp16 step (csrc/hash_bwd_percorner.h); both run-record kernels are built on the run-combining core of csrc/hash_bwd_common.h, and
+csrc/hash_encode.hip is the translation unit that includes the three.
 
-CPU part: none of the stage's kernels that the fp32 step launches may spill or use AGPRs (device-only compile, as tests/test_abi.py's field-kernel guard).
+CPU part: none of the stage's kernels that the fp32 or the fp16 step launches may spill or use AGPRs (device-only compile, as tests/test_abi.py's field-kernel guard).
 GPU part: the run-record kernel the step launches (its V2 form) against the form it replaced (NGP_HASH_BWD_RUNS=0), byte for byte - the accumulation is exact integer
 arithmetic over records whose values are the same fp32 sums, so there is no tolerance."""
 import os
@@ -16,7 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_hash_bwd_stage_kernels_do_not_spill():
     """k_bin_runs2 (the form the step launches: last template argument true), k_bin_pairs<float, ...> and k_bin_accumulate2<float, true | false>: ScratchSize == 0 and
     AGPRs == 0, both layouts.  The earlier form of k_bin_runs2 that NGP_HASH_BWD_RUNS=0 still selects for A/B runs (last argument false, 48-52 B of scratch per
-    lane) is not launched by the step and is not held to this."""
+    lane) is not launched by the step and is not held to this.  The fp16 step's kernels, which share the run-combining core, are held to the same:
+    k_bin_records_runs<*, *, 4> (four instantiations), k_bin_records<*, *> (four) and k_bin_accumulate<*, *, *> (six)."""
     import shutil
     if not shutil.which("/opt/rocm/bin/hipcc"):
         pytest.skip("hipcc not installed")
@@ -35,7 +38,11 @@ def test_hash_bwd_stage_kernels_do_not_spill():
     pairs = [r for r in rows if r["name"].startswith("_Z11k_bin_pairsIf")]
     acc = [r for r in rows if r["name"].startswith("_Z17k_bin_accumulate2IfLb")]
     assert len(runs) == 2 and len(pairs) == 4 and len(acc) == 2, [r["name"] for r in rows]
-    for r in runs + pairs + acc:
+    rec_runs = [r for r in rows if re.match(r"_Z18k_bin_records_runsI\w+Li[01]ELi4EE", r["name"])]
+    rec = [r for r in rows if r["name"].startswith("_Z13k_bin_recordsI")]
+    acc1 = [r for r in rows if r["name"].startswith("_Z16k_bin_accumulateI")]
+    assert len(rec_runs) == 4 and len(rec) == 4 and len(acc1) == 6, [r["name"] for r in rows]
+    for r in runs + pairs + acc + rec_runs + rec + acc1:
         print(r)
         assert r["ScratchSize [bytes/lane]"] == 0, r
         assert r["AGPRs"] == 0, r

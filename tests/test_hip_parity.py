@@ -756,7 +756,7 @@ def test_hash_bwd_workspace_strided_positions_n_valid_and_zero_rows(H, dtype):
 @pytest.mark.parametrize("dtype", [np.float16, np.float32])
 def test_hash_bwd_bin_overflow_spills_exactly(H, dtype, cluster):
     """A clustered batch drives a few bins far beyond their record capacity (n/2): the surplus goes to the shared spill list and is folded in by the bins'
-    owners - same result as the oracle, still bit-reproducible, no float atomics (hash_encode.hip k_bin_records[_runs] / k_bin_accumulate).
+    owners - same result as the oracle, still bit-reproducible, no float atomics (hash_bwd_percorner.h k_bin_records[_runs] / k_bin_accumulate).
     one_cell: every sample inside one cell of the finest level (the fine, hashed levels overflow; on the coarse levels the runs collapse to a few records).
     one_bin_of_a_dense_level: every sample in a DIFFERENT cell of dense level 4 whose lowest corner lives in bin 5 of the interleaved entry->bin map, in random
     order (no runs to combine): >= 20000 records for a bin of capacity 10000, through the run-combining record kernel's direct / spill stores."""

@@ -283,7 +283,7 @@ def test_jittor_pickle_container_round_trip(tmp_path):
 
 
 def test_fixed_point_conversion_equals_round_half_even():
-    """(r4) `fixed_rn` (csrc/hash_encode.hip): contribution * 2^k -> nearest 64-bit integer, ties to even, in seven instructions instead of __float2ll_rn's generic expansion.
+    """(r4) `fixed_rn` (csrc/hash_bwd_common.h): contribution * 2^k -> nearest 64-bit integer, ties to even, in seven instructions instead of __float2ll_rn's generic expansion.
     The accumulate kernel's exactness rests on it; the same function compiled for the host is held to Python's exact arithmetic here (c * 2^k is exact in a double)."""
     import ctypes as C
     from jnerf_amd import _lib
@@ -363,7 +363,7 @@ def test_edge_record_multiplication_order_carries_the_references_error_bound():
 
 @pytest.mark.parametrize("aabb_scale", [1, 4])
 def test_region_path_bin_mapping_is_a_bijection_on_every_level(aabb_scale):
-    """(r4) entry -> (bin, slot) -> entry of the region kernels / k_bin_accumulate2 (csrc/hash_encode.hip: bin2_of, local2_of, entry2_of), compiled for the host: every entry of every
+    """(r4) entry -> (bin, slot) -> entry of the region kernels / k_bin_accumulate2 (csrc/hash_bwd_regions.h: bin2_of, local2_of, entry2_of), compiled for the host: every entry of every
     level maps to a slot inside the range its bin's accumulate workgroup zeroes and writes out, no two entries share a slot, and the way back is exact - small (dense) levels are dealt to
     the 128 bins in interleaved groups of eight, full 2^19-entry levels in 4096-entry slices"""
     import ctypes as C

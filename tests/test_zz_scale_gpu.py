@@ -1,5 +1,5 @@
 """-m gpu: the hash-grid backward's region path (round 4) at a batch LARGER than anything the training configurations use - more than 512 record regions per level, so the
-accumulate kernel's gather walks its segment table in two blocks (csrc/hash_encode.hip: gather_flat's `w0` loop) and the run kernel fills 293 regions.
+accumulate kernel's gather walks its segment table in two blocks (csrc/hash_bwd_regions.h: gather_flat's `w0` loop) and the run kernel fills 293 regions.
 
 The one-block case (n <= 2^19 samples) is what every other test and the bench exercise.  First hardware run: the driver's round-4 end-of-round suite (GPUTEST_r04.json: XPASS) - the
 xfail marker it carried until then is gone, a regression now fails the suite."""

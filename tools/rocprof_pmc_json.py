@@ -22,7 +22,7 @@ def per_kernel(db, counter):
         k = name[m.end():m.end() + int(m.group(1))]
         if not k.startswith("k_"):
             continue
-        # (r6) template instantiations that bench.py's brackets know under names of their own (NGP_LAUNCH registers the macro alias, csrc/hash_encode.hip)
+        # (r6) template instantiations that bench.py's brackets know under names of their own (NGP_LAUNCH registers the alias, csrc/hash_encode.hip)
         rest = name[m.end() + int(m.group(1)):]
         if k == "k_bin_accumulate2" and rest.startswith("IfLb1E"):
             k = "k_bin_accumulate2_adam"
