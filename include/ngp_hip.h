@@ -17,6 +17,7 @@
  */
 #ifndef NGP_HIP_H
 #define NGP_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -266,6 +267,21 @@ int ngp_neus_composite_fwd(void *stream, uint32_t n_rays, uint32_t n, uint32_t n
 int ngp_neus_composite_bwd(void *stream, uint32_t n_rays, uint32_t n, uint32_t n_total, const float *sdf, const float *cosv, const float *dists, const float *inv_s,
                            const float *color, const float *inside, const float *bg_alpha, const float *bg_color, float cos_anneal_ratio,
                            const float *g_color, const float *g_weights, float *d_sdf, float *d_cos, float *d_inv_s_partial, float *d_color, float *d_bg_alpha, float *d_bg_color);
+
+/* ---- iso-surface extraction: marching tetrahedra on a lattice u f32[X][Y][Z] (z fastest), the device counterpart of jnerf_amd/utils/isosurface.py::marching_tetrahedra
+ * (what the reference gets from mcubes.marching_cubes, models/samplers/neus_render/renderer.py:32 and tools/extract_mesh.py:76).  A point is above iff u > threshold; one
+ * vertex per lattice edge of the six-tetrahedra decomposition whose ends lie on different sides, in ascending (lower end, upper end) flat-id order, f64 lattice-index
+ * coordinates; triangles cube by cube, int32 indices, normals from above to below.  Two calls, because the caller allocates the outputs:
+ *   ngp_iso_count fills `workspace` (>= ngp_iso_workspace_bytes(X, Y, Z) bytes, 16-byte aligned; ~6 bytes per lattice point) and writes {vertices, triangles} to `counts`
+ *     (DEVICE u64[2]);
+ *   ngp_iso_emit, given the workspace ngp_iso_count left for the same lattice and threshold and the two counts, writes vertices f64[n_vertices,3] and
+ *     triangles i32[n_triangles,3].  It completes the workspace (per-point vertex bases) and never writes past the counts it was given.
+ * Every dimension >= 2 (else NGP_E_ARG), X*Y*Z <= 2^31 - 1 and either count <= 2^31 - 1 (else NGP_E_CAPACITY); ngp_iso_workspace_bytes returns 0 for a shape the calls refuse.
+ * Output order is a function of the lattice alone: slots come from scans, not from atomics. */
+size_t ngp_iso_workspace_bytes(uint32_t X, uint32_t Y, uint32_t Z);
+int ngp_iso_count(void *stream, const float *u, uint32_t X, uint32_t Y, uint32_t Z, double threshold, void *workspace, size_t workspace_bytes, uint64_t *counts);
+int ngp_iso_emit(void *stream, const float *u, uint32_t X, uint32_t Y, uint32_t Z, double threshold, const void *workspace, size_t workspace_bytes, uint64_t n_vertices,
+                 uint64_t n_triangles, double *vertices, int32_t *triangles);
 
 /* ---- one training iteration's launch sequence, issued from native code -------------------------------------------------------------------
  * The body of Runner.train for one already-sampled batch (runner/runner.py:71-76: model(pos, dir) -> sampler.rays2rgb -> HuberLoss ->

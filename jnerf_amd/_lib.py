@@ -121,6 +121,9 @@ SIGNATURES = {
     "ngp_dp_plan": (C.c_int, [_vp, _u64, _i32, _i32, _i32, C.POINTER(NgpDpPlan)]),
     "ngp_dp_allgather": (C.c_int, [_vp, _vp, C.POINTER(NgpDpPlan), _i32, C.POINTER(_vp), C.POINTER(_i32)]),
     "ngp_generate_rays": (C.c_int, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ngp_iso_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32]),
+    "ngp_iso_count": (C.c_int, [_vp, _vp, _u32, _u32, _u32, C.c_double, _vp, C.c_size_t, _vp]),
+    "ngp_iso_emit": (C.c_int, [_vp, _vp, _u32, _u32, _u32, C.c_double, _vp, C.c_size_t, _u64, _u64, _vp, _vp]),
 }
 
 

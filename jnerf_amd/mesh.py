@@ -19,20 +19,21 @@ mesh-origin.ply is NOT mirrored."""
 import os
 import numpy as np
 import torch
-from .utils.isosurface import marching_tetrahedra, write_ply
+from .utils.isosurface import marching_tetrahedra, marching_tetrahedra_device, write_ply
 
 RAY_BACKOFF = 0.2                    # extract_mesh.py:121
 LATTICE_CHUNK = 512 * 512 * 512      # extract_mesh.py:44: lattice points per slab
 
 
 @torch.no_grad()
-def occupancy_lattice(model, resolution, device, batch=4096 * 128):
-    """int32 [N, N, N] (indexed [ix, iy, iz]) = trunc(max(log-density, 0)) at the lattice points linspace(0, 1, N)^3  (extract_mesh.py:41-70)"""
+def occupancy_lattice(model, resolution, device, batch=4096 * 128, to_host=True):
+    """int32 [N, N, N] (indexed [ix, iy, iz]) = trunc(max(log-density, 0)) at the lattice points linspace(0, 1, N)^3  (extract_mesh.py:41-70): a numpy array, or with
+    to_host=False the device tensor (no host array is built)"""
     N = int(resolution)
     step = max(min(LATTICE_CHUNK // (N * N), N), 1)
     assert N % step == 0, "the resolution must be a multiple of the slab thickness (extract_mesh.py:46)"
     axis = torch.linspace(0.0, 1.0, N, device=device)
-    out = np.empty((N, N, N), dtype=np.int32)
+    out = np.empty((N, N, N), dtype=np.int32) if to_host else torch.empty((N, N, N), dtype=torch.int32, device=device)
     for k in range(0, N, step):
         x = axis[k:k + step]
         xyz = torch.stack(torch.meshgrid(x, axis, axis, indexing="ij"), -1).reshape(-1, 3)
@@ -41,7 +42,7 @@ def occupancy_lattice(model, resolution, device, batch=4096 * 128):
             pos = xyz[i:i + batch].contiguous()
             sigma = model(pos, torch.zeros_like(pos))[:, -1].float()
             slab[i:i + batch] = sigma.clamp_min(0.0).to(torch.int32)           # .int(): truncation toward zero
-        out[k:k + step] = slab.view(step, N, N).cpu().numpy()
+        out[k:k + step] = slab.view(step, N, N).cpu().numpy() if to_host else slab.view(step, N, N)
     return out
 
 
@@ -111,13 +112,21 @@ def vertex_colors(runner, vertices, outward):
     return (rgb * 255 + 0.5).clamp(0, 255).to(torch.uint8).cpu().numpy()
 
 
-def extract_mesh(runner, resolution=512, smooth=False, save_dir=None, log=print):
-    """the whole of tools/extract_mesh.py after `runner.load_ckpt`; returns (vertices f32 [nv, 3] in the unit cube, triangles i32 [nt, 3], colours u8 [nv, 3])"""
+def extract_mesh(runner, resolution=512, smooth=False, save_dir=None, log=print, iso="host"):
+    """the whole of tools/extract_mesh.py after `runner.load_ckpt`; returns (vertices f32 [nv, 3] in the unit cube, triangles i32 [nt, 3], colours u8 [nv, 3]).
+    iso="device": the lattice stays on the GPU and the iso-surface comes from csrc/iso_surface.hip (marching_tetrahedra_device) - the same vertices and triangle set;
+    only they come to the host."""
+    if iso not in ("host", "device"):
+        raise ValueError(f"iso must be 'host' or 'device', not {iso!r}")
+    if iso == "device" and smooth:
+        raise ValueError("iso='device' with smooth=True is not supported: the smoothing filter runs on the host (scipy); use iso='host'")
     save_dir = save_dir or runner.save_path
     os.makedirs(save_dir, exist_ok=True)
     N = int(resolution)
-    occ = occupancy_lattice(runner.model, N, runner.dataset["train"].device)
-    if smooth:
+    occ = occupancy_lattice(runner.model, N, runner.dataset["train"].device, to_host=iso == "host")
+    if iso == "device":
+        verts, tris = (t.cpu().numpy() for t in marching_tetrahedra_device(occ, 0.5))
+    elif smooth:
         verts, tris = marching_tetrahedra(smooth_occupancy(occ > 0), 0.0)
     else:
         verts, tris = marching_tetrahedra(occ, 0.5)

@@ -12,26 +12,31 @@ from .neus_network import safe_clip, jt_norm
 from .utils.registry import SAMPLERS
 
 
-def extract_fields(bound_min, bound_max, resolution, query_func, block=64):
-    """renderer.py:11-26: query_func on a resolution^3 lattice, 64^3 points at a time"""
+def extract_fields(bound_min, bound_max, resolution, query_func, block=64, to_host=True):
+    """renderer.py:11-26: query_func on a resolution^3 lattice, 64^3 points at a time; float32 numpy array, or with to_host=False a device tensor"""
     axes = [torch.linspace(float(bound_min[d]), float(bound_max[d]), resolution, device=bound_min.device).split(block) for d in range(3)]
-    u = np.zeros([resolution] * 3, dtype=np.float32)
+    u = np.zeros([resolution] * 3, dtype=np.float32) if to_host else torch.zeros([resolution] * 3, dtype=torch.float32, device=bound_min.device)
     with torch.no_grad():
         for xi, xs in enumerate(axes[0]):
             for yi, ys in enumerate(axes[1]):
                 for zi, zs in enumerate(axes[2]):
                     xx, yy, zz = torch.meshgrid(xs, ys, zs, indexing="ij")
                     pts = torch.stack([xx.reshape(-1), yy.reshape(-1), zz.reshape(-1)], -1)
-                    val = query_func(pts).reshape(len(xs), len(ys), len(zs)).float().cpu().numpy()
+                    val = query_func(pts).reshape(len(xs), len(ys), len(zs)).float()
+                    val = val.cpu().numpy() if to_host else val
                     u[xi * block: xi * block + len(xs), yi * block: yi * block + len(ys), zi * block: zi * block + len(zs)] = val
     return u
 
 
-def extract_geometry(bound_min, bound_max, resolution, threshold, query_func):
-    """renderer.py:29-38 (mcubes.marching_cubes there; PyMCubes is not installed here: utils/isosurface.py's marching tetrahedra on the same lattice)"""
-    from .utils.isosurface import marching_tetrahedra
-    u = extract_fields(bound_min, bound_max, resolution, query_func)
-    vertices, triangles = marching_tetrahedra(u, threshold)
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, device=False):
+    """renderer.py:29-38 (mcubes.marching_cubes there; PyMCubes is not installed here: utils/isosurface.py's marching tetrahedra on the same lattice).
+    device=True: the lattice stays on the GPU and the surface comes from csrc/iso_surface.hip; the results are numpy arrays either way."""
+    from .utils.isosurface import marching_tetrahedra, marching_tetrahedra_device
+    u = extract_fields(bound_min, bound_max, resolution, query_func, to_host=not device)
+    if device:
+        vertices, triangles = (t.cpu().numpy() for t in marching_tetrahedra_device(u, threshold))
+    else:
+        vertices, triangles = marching_tetrahedra(u, threshold)
     b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
     vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
     return vertices, triangles
@@ -227,5 +232,5 @@ class NeuSRenderer:
                 "weight_sum": weights.sum(-1, keepdim=True), "weight_max": weights.max(-1, keepdim=True)[0], "sdf": ret_fine["sdf"], "gradients": ret_fine["gradients"],
                 "alpha": ret_fine["alpha"], "z_vals": z_vals, "weights": weights, "gradient_error": ret_fine["gradient_error"], "inside_sphere": ret_fine["inside_sphere"]}
 
-    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0):
-        return extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold, query_func=lambda pts: -self.sdf_network.sdf(pts))
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, device=False):
+        return extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold, query_func=lambda pts: -self.sdf_network.sdf(pts), device=device)

@@ -186,11 +186,11 @@ class NeuSRunner:
         rgb, _, _ = self._render_batches(rays_o, rays_d, want_geometry=False)
         return (np.concatenate(rgb, 0).reshape([H, W, 3]) * 256).clip(0, 255).astype(np.uint8)
 
-    def validate_mesh(self, world_space=False, resolution=64, threshold=0.0):
+    def validate_mesh(self, world_space=False, resolution=64, threshold=0.0, device=False):
         from .utils.isosurface import write_ply
         bound_min = torch.tensor(self.dataset.object_bbox_min, dtype=torch.float32, device=self.device)
         bound_max = torch.tensor(self.dataset.object_bbox_max, dtype=torch.float32, device=self.device)
-        vertices, triangles = self.renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold)
+        vertices, triangles = self.renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold, device=device)
         os.makedirs(os.path.join(self.base_exp_dir, f"meshes_{resolution}"), exist_ok=True)
         if world_space:
             vertices = vertices * self.dataset.scale_mats_np[0][0, 0] + self.dataset.scale_mats_np[0][:3, 3][None]

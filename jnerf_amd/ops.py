@@ -509,6 +509,39 @@ def generate_rays(pixel_index, W, H, focal, metadata, xforms, images=None, bg=No
     return img, o, d, target
 
 
+# ------------------------------------------------------------------ iso-surface (csrc/iso_surface.hip)
+def iso_workspace_bytes(shape):
+    """bytes of workspace iso_count / iso_emit need for an [X, Y, Z] lattice (0: a shape they refuse)"""
+    X, Y, Z = (int(s) for s in shape)
+    return int(L.lib().ngp_iso_workspace_bytes(X, Y, Z))
+
+
+def iso_count(u, threshold, workspace, counts=None):
+    """classify + scan of a float32 lattice u [X, Y, Z]: fills `workspace` (uint8, >= iso_workspace_bytes(u.shape)) and returns the device int64[2] = (vertices, triangles)"""
+    assert u.dtype == torch.float32 and u.dim() == 3 and u.is_contiguous(), (u.dtype, u.shape)
+    assert workspace.dtype == torch.uint8
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int64, device=u.device)
+    X, Y, Z = u.shape
+    check(L.lib().ngp_iso_count(_stream(), _p(u), X, Y, Z, float(threshold), _p(workspace), workspace.numel(), _p(counts)), "ngp_iso_count")
+    return counts
+
+
+def iso_emit(u, threshold, workspace, n_vertices, n_triangles, vertices=None, triangles=None):
+    """vertices f64 [nv, 3] (lattice-index coordinates) and triangles i32 [nt, 3] of the lattice iso_count classified into `workspace` with the same threshold"""
+    assert u.dtype == torch.float32 and u.dim() == 3 and u.is_contiguous(), (u.dtype, u.shape)
+    n_vertices, n_triangles = int(n_vertices), int(n_triangles)
+    if vertices is None:
+        vertices = torch.empty((n_vertices, 3), dtype=torch.float64, device=u.device)
+    if triangles is None:
+        triangles = torch.empty((n_triangles, 3), dtype=torch.int32, device=u.device)
+    assert vertices.dtype == torch.float64 and vertices.is_contiguous() and vertices.numel() >= 3 * n_vertices
+    assert triangles.dtype == torch.int32 and triangles.is_contiguous() and triangles.numel() >= 3 * n_triangles
+    X, Y, Z = u.shape
+    check(L.lib().ngp_iso_emit(_stream(), _p(u), X, Y, Z, float(threshold), _p(workspace), workspace.numel(), n_vertices, n_triangles, _p(vertices), _p(triangles)), "ngp_iso_emit")
+    return vertices, triangles
+
+
 def flag_signal(flag, value):
     """one-thread launch on the current stream: *flag = value (device int32 / uint32 scalar view), see ngp_flag_signal"""
     check(L.lib().ngp_flag_signal(_stream(), _p(flag), int(value) & 0xFFFFFFFF), "ngp_flag_signal")

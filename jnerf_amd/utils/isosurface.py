@@ -99,6 +99,34 @@ def marching_tetrahedra(u, threshold=0.0):
     return vertices, faces.astype(np.int64)
 
 
+_device_workspaces = {}          # (device, shape) -> uint8 tensor: the classify pass's masks, counts and scan bases
+
+
+def marching_tetrahedra_device(u, threshold=0.0):
+    """marching_tetrahedra on the GPU (csrc/iso_surface.hip: ngp_iso_count + ngp_iso_emit).  u: CUDA tensor [X, Y, Z], float32 (integer tensors are converted, which is
+    exact for occupancy values).  Returns DEVICE tensors (vertices f64 [nv, 3] in lattice-index coordinates, triangles i32 [nt, 3]): the host function's vertices, in
+    its order (up to a few float64 roundings: every edge is interpolated from its lower end), and its triangles, cube by cube.  One host read-back: the two counts."""
+    import torch
+    from .. import ops
+    assert u.is_cuda and u.dim() == 3, "a [X, Y, Z] device tensor (the host function is marching_tetrahedra)"
+    empty = (torch.zeros((0, 3), dtype=torch.float64, device=u.device), torch.zeros((0, 3), dtype=torch.int32, device=u.device))
+    if min(u.shape) < 2:
+        return empty
+    u = u.to(torch.float32).contiguous()
+    key = (u.device, tuple(u.shape))
+    ws = _device_workspaces.get(key)
+    if ws is None:
+        n_bytes = ops.iso_workspace_bytes(u.shape)
+        if n_bytes == 0:
+            raise ValueError(f"a lattice of {tuple(u.shape)} has more than 2^31 - 1 points")
+        _device_workspaces.clear()                                           # one shape at a time: a 1024^3 workspace is 6.4 GB
+        ws = _device_workspaces[key] = torch.empty(n_bytes, dtype=torch.uint8, device=u.device)
+    nv, nt = ops.iso_count(u, threshold, ws).tolist()
+    if nt == 0:
+        return empty
+    return ops.iso_emit(u, threshold, ws, nv, nt)
+
+
 def write_ply(path, vertices, triangles, colors=None):
     """binary little-endian PLY (what trimesh's export writes for a .ply path); `colors` uint8 [nv, 3] adds the uchar red / green / blue vertex properties that
     tools/extract_mesh.py:145-156 writes through plyfile"""
