@@ -29,6 +29,13 @@ __device__ __forceinline__ float calc_dt(float t, const MarchParams &p) {       
 	if (p.const_dt) return min_cone_stepsize() * 0.5;
 	return clampf(t * p.cone_angle, min_cone_stepsize(), max_cone_stepsize(p.cascades));
 }
+// calc_dt where the stepping is a compile-time fact (k_march_wave<., CONST_DT>): the same expressions without the test of p.const_dt.  With the constant step dt is a literal,
+// and mip_from_dt folds to mip_from_pos (dt * 256 < 1).
+template <bool CONST_DT>
+__device__ __forceinline__ float calc_dt_as(float t, const MarchParams &p) {
+	if (CONST_DT) return min_cone_stepsize() * 0.5;
+	return clampf(t * p.cone_angle, min_cone_stepsize(), max_cone_stepsize(p.cascades));
+}
 __device__ __forceinline__ int mip_from_pos(const float pos[3], int cascades) {    // ray_sampler_header.h:60-66
 	int e;
 	float m = fmaxf(fmaxf(fabsf(pos[0] - 0.5f), fabsf(pos[1] - 0.5f)), fabsf(pos[2] - 0.5f));
@@ -220,7 +227,8 @@ __global__ __launch_bounds__(128) void k_march_count(uint32_t n_rays, MarchParam
 //           (a0 + i*q)*U - exact integer arithmetic, bit-identical to the serial sum - and only the 1-3 steps around a binade crossing are real fp32 adds.
 //           (Cone stepping has no closed form: lane 0 runs the recurrence.)
 //   eval  : lane = candidate (position, box test, mip level, occupancy bit, skip target and - by a lower-bound search in the LDS chain - the candidate nx the
-//           visit would continue at): one memory round trip per 64 candidates instead of one per visited candidate;
+//           visit would continue at), in two passes - addresses and the byte loads of all four windows, then everything that needs the bytes: one memory round
+//           trip per ROUND of 256 candidates instead of one per visited candidate;
 //   walk  : the visited candidates are the orbit of the start under c -> nx[c].  G[c] = "no earlier candidate of this round skips past c" (prefix-max of nx,
 //           one wavefront scan per window) is a guess that is right unless float fuzz makes two candidates of one empty cell land differently; it is CHECKED
 //           exactly - every member of G must continue at the next member of G - and if the check holds G IS the orbit (induction from the start).  Otherwise
@@ -229,14 +237,25 @@ __global__ __launch_bounds__(128) void k_march_count(uint32_t n_rays, MarchParam
 //           north_star.
 // No workgroup-level synchronisation at all: a ray's rounds depend on nothing but the ray.  History (ngp_base.py sampling, 7.8 k rays x 33 samples, alone on the
 // GPU): serial 665 us; four rays per workgroup with one THREAD per ray for the chain and the walk and four barriers per round (round 2's first version) 169 us -
-// those single-thread phases of the eight workgroups resident on a CU queued up behind each other; this kernel 94 us.
+// those single-thread phases of the eight workgroups resident on a CU queued up behind each other; one wavefront per ray 94 us; this kernel - the round's four byte
+// loads in flight together, the walk's scans as DPP, the skip search's first probe as one two-address read, the step a compile-time fact - 72 us, same bits
+// (profiles/r09_marcher.md: it is bound by vector-instruction issue, 1304 -> 1057 vector instructions per round of the loop, 74 -> 54 VGPRs).
 #define MC_WIN 64u           // candidates per wavefront-wide window
 
-__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v, uint32_t lane) {
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) { const uint32_t y = __shfl_up(v, off); if (lane >= (uint32_t)off) v = max(v, y); }
+// Cross-lane steps of the walk as DPP operands of the vector ALU (no trip through the LDS pipe, which __shfl_up takes).  A lane whose source lies outside its row of 16
+// (or outside the wavefront), and every row not in ROW_MASK, reads 0 - the identity of an unsigned max.
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false); }
+__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
+	v = max(v, dpp_or_zero<0x111>(v));                        // row_shr:1, 2, 4, 8: inclusive scan inside each row of 16 lanes
+	v = max(v, dpp_or_zero<0x112>(v));
+	v = max(v, dpp_or_zero<0x114>(v));
+	v = max(v, dpp_or_zero<0x118>(v));
+	v = max(v, dpp_or_zero<0x142, 0xa>(v));                   // row_bcast:15 into rows 1 and 3: the row before
+	v = max(v, dpp_or_zero<0x143, 0xc>(v));                   // row_bcast:31 into rows 2 and 3: the lower half
 	return v;
 }
+__device__ __forceinline__ uint32_t wave_shr1_or_zero(uint32_t v) { return dpp_or_zero<0x138>(v); }      // wave_shr:1: lane l reads lane l - 1, lane 0 reads 0
 __device__ __forceinline__ unsigned long long bits_below(uint32_t n) { return n >= 64u ? ~0ull : ((1ull << n) - 1ull); }
 
 template <uint32_t NW, bool CONST_DT>
@@ -273,7 +292,7 @@ __global__ __launch_bounds__(64) void k_march_wave(uint32_t n_rays, MarchParams 
 		__syncthreads();                                      // (one wavefront: orders this round's LDS writes after the last round's reads; also publishes mlut)
 		// ---- chain: tch[0 .. NC] = the next NC + 1 values of the ray's fixed sequence
 		if (CONST_DT) {
-			const float dtc = calc_dt(t_round, p);
+			const float dtc = calc_dt_as<true>(t_round, p);
 			uint32_t k = 0; float t = t_round;
 			while (k <= NC) {
 				int e; (void)frexpf(t, &e);
@@ -314,23 +333,21 @@ __global__ __launch_bounds__(64) void k_march_wave(uint32_t n_rays, MarchParams 
 			for (int w = (int)NW - 1; w >= 0; --w) { const unsigned long long m = __ballot(!(tl[w] < pend)); if (m) s = (uint32_t)w * MC_WIN + (uint32_t)__builtin_ctzll(m); }
 			if (s == NC) continue;                            // the whole round lies before the target
 		}
-		// ---- eval: lane = candidate, NW candidates per lane
-		unsigned long long INm[NW], OCCm[NW];
-		uint32_t nxw[NW]; float tgt[NW];
+		// ---- eval: lane = candidate, NW candidates per lane, in two passes so that the round has ONE memory round trip.
+		// Pass 1 issues the occupancy-byte loads of all the round's windows; what pass 2 needs of a candidate besides the byte is one word: 0 outside the box,
+		// else 0x100 | mip << 4 | the bit's number in the byte.  (The position is cheaper to compute again than to keep: same expression, same bits.)
+		// The loads stand together behind the address arithmetic of all windows (a candidate outside the box, or before the start, reads byte 0 and ignores it): issued
+		// between the windows' arithmetic they end up waited for there, whenever the allocator puts a byte in flight next to a register of that arithmetic.
+		uint32_t occb[NW], meta[NW], boff[NW];
 #pragma unroll
 		for (uint32_t w = 0; w < NW; ++w) {
-			const uint32_t self = w * MC_WIN + lane;
-			nxw[w] = 0; tgt[w] = 0.f; INm[w] = 0ull; OCCm[w] = 0ull;
+			boff[w] = 0u; meta[w] = 0u;
 			if ((w + 1u) * MC_WIN <= s) continue;             // (wave-uniform) window before the start
 			float pos[3];
 #pragma unroll
 			for (int k = 0; k < 3; ++k) pos[k] = o[k] + tl[w] * d[k];
-			const bool inside = contains(p, pos);
-			bool occ = false;
-			float target = 0.f;
-			uint32_t nx = self + 1u;
-			if (inside) {
-				const float dt = calc_dt(tl[w], p);
+			if (contains(p, pos)) {
+				const float dt = calc_dt_as<CONST_DT>(tl[w], p);
 				const uint32_t mip = (uint32_t)mip_from_dt(dt, pos, p.cascades);
 				const float mip_scale = scalbnf(1.0f, -(int)mip);                 // occupied_at (ray_sampler_header.h:755-776), morton code from the LDS table
 				uint32_t c[3];
@@ -341,24 +358,44 @@ __global__ __launch_bounds__(64) void k_march_wave(uint32_t n_rays, MarchParams 
 					c[k] = (uint32_t)min(max(ci, 0), (int)NGP_GRIDSIZE - 1);
 				}
 				const uint32_t idx = mlut[c[0]] | (mlut[c[1]] << 1) | (mlut[c[2]] << 2);
-				occ = bitfield[idx / 8 + (NGP_GRIDSIZE * NGP_GRIDSIZE * NGP_GRIDSIZE * mip) / 8] & (1 << (idx % 8));
-				if (!occ) {                                              // next_voxel_target with the per-ray constants (same expressions: x / 2^k == x * 2^-k exactly)
-					const uint32_t res = NGP_GRIDSIZE >> mip;
-					const float resf = (float)res, inv_res = scalbnf(1.0f, (int)mip - 7);      // 1 / res, exactly: res = 128 >> mip is a power of two
-					float t3[3];
+				boff[w] = idx / 8 + (NGP_GRIDSIZE * NGP_GRIDSIZE * NGP_GRIDSIZE * mip) / 8;
+				meta[w] = 0x100u | (mip << 4) | (idx % 8);
+			}
+		}
 #pragma unroll
-					for (int k = 0; k < 3; ++k) { const float q = resf * pos[k]; t3[k] = (floorf(q + 0.5f + hs[k]) - q) * idir[k]; }
-					const float tt = fminf(fminf(t3[0], t3[1]), t3[2]);
-					target = tl[w] + fmaxf(tt * inv_res, 0.0f);
-					// the skip lands on the first candidate m > self with !(t_m < target): estimate from the local step, settle with LDS probes (NC = beyond this round)
-					const float est = (target - tl[w]) * __frcp_rn(dt);                        // (only where the search below STARTS: it settles on the same candidate from any start)
-					uint32_t g = self + 1u;
-					if (est > 1.0f) g = est >= (float)NC ? NC : self + (uint32_t)est;
-					if (g > NC) g = NC;
-					while (g > self + 1u && !(tch[g - 1u] < target)) --g;
-					while (g < NC && tch[g] < target) ++g;
-					nx = g;
-				}
+		for (uint32_t w = 0; w < NW; ++w) occb[w] = bitfield[boff[w]];
+		unsigned long long INm[NW], OCCm[NW];
+		uint32_t nxw[NW]; float tgt[NW];
+#pragma unroll
+		for (uint32_t w = 0; w < NW; ++w) {
+			const uint32_t self = w * MC_WIN + lane;
+			nxw[w] = 0; tgt[w] = 0.f; INm[w] = 0ull; OCCm[w] = 0ull;
+			if ((w + 1u) * MC_WIN <= s) continue;
+			const bool inside = meta[w] != 0u;
+			const bool occ = inside && ((occb[w] >> (meta[w] & 7u)) & 1u);
+			float target = 0.f;
+			uint32_t nx = self + 1u;
+			if (inside && !occ) {                                        // next_voxel_target with the per-ray constants (same expressions: x / 2^k == x * 2^-k exactly)
+				const uint32_t mip = (meta[w] >> 4) & 15u;
+				const float resf = (float)(NGP_GRIDSIZE >> mip), inv_res = scalbnf(1.0f, (int)mip - 7);      // 1 / res, exactly: res = 128 >> mip is a power of two
+				float t3[3];
+#pragma unroll
+				for (int k = 0; k < 3; ++k) { const float q = resf * (o[k] + tl[w] * d[k]); t3[k] = (floorf(q + 0.5f + hs[k]) - q) * idir[k]; }
+				const float tt = fminf(fminf(t3[0], t3[1]), t3[2]);
+				target = tl[w] + fmaxf(tt * inv_res, 0.0f);
+				// the skip lands on the first candidate m > self with !(t_m < target): estimate from the local step, settle with LDS probes (NC = beyond this round)
+				// (only where the search below STARTS - it settles on the same candidate from any start: the hardware's approximate reciprocal will do for a varying step)
+				const float dt = calc_dt_as<CONST_DT>(tl[w], p);
+				const float est = (target - tl[w]) * (CONST_DT ? 1.0f / dt : __builtin_amdgcn_rcpf(dt));
+				uint32_t g = self + 1u;
+				if (est > 1.0f) g = est >= (float)NC ? NC : self + (uint32_t)est;
+				if (g > NC) g = NC;
+				// both neighbours of the estimate in one two-address LDS read; the loops are the two `while`s of a lower-bound search, entered only where their first
+				// test (made here) holds.  A step down ends at a g with !(tch[g] < target), so the upward loop could not run after it: else-if.
+				const float below = tch[g - 1u], at = tch[g];
+				if (g > self + 1u && !(below < target)) { do --g; while (g > self + 1u && !(tch[g - 1u] < target)); }
+				else if (g < NC && at < target) { do ++g; while (g < NC && tch[g] < target); }
+				nx = g;
 			}
 			INm[w] = __ballot(inside); OCCm[w] = __ballot(occ);
 			nxw[w] = nx; tgt[w] = target;
@@ -370,9 +407,8 @@ __global__ __launch_bounds__(64) void k_march_wave(uint32_t n_rays, MarchParams 
 #pragma unroll
 			for (uint32_t w = 0; w < NW; ++w) {
 				const uint32_t self = w * MC_WIN + lane;
-				const uint32_t incl = wave_incl_max(self >= s ? nxw[w] : 0u, lane);
-				const uint32_t up = __shfl_up(incl, 1);
-				const uint32_t ex = max(carry, lane ? up : 0u);
+				const uint32_t incl = wave_incl_max(self >= s ? nxw[w] : 0u);
+				const uint32_t ex = max(carry, wave_shr1_or_zero(incl));
 				G[w] = __ballot(self >= s && (self == s || ex == self));
 				carry = max(carry, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63));
 			}
@@ -420,7 +456,7 @@ __global__ __launch_bounds__(64) void k_march_wave(uint32_t n_rays, MarchParams 
 					for (int w = (int)NW - 1; w >= 0; --w) {
 						if (G[w]) {
 							const uint32_t ll = 63u - (uint32_t)__builtin_clzll(G[w]);
-							if (!((OCCm[w] >> ll) & 1ull)) pend = __shfl(tgt[w], (int)ll);
+							if (!((OCCm[w] >> ll) & 1ull)) pend = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tgt[w]), (int)ll));      // (ll comes from a ballot: wave-uniform)
 							break;
 						}
 					}
