@@ -9,7 +9,8 @@
 //  * ... and the blockIdx -> (level, chunk) map is XCD-aware: the dispatcher places block b on XCD b%8 and each XCD has a
 //    private 4 MiB L2, so XCD x is handed level 15-x for ALL sample chunks first and level x afterwards.  A level's table
 //    slice is then fetched from HBM/Infinity-Cache once per XCD and served out of that XCD's L2 for the rest of the pass
-//    instead of being bounced between eight L2s.  This mapping affects speed only, never results.
+//    instead of being bounced between eight L2s.  This mapping affects speed only, never results.  (r10) k_hash_fwd_x2, the fp32 forward, pairs the XCDs instead - XCD x and
+//    7 - x share four levels - because "15-x, then x" left seven XCDs waiting for XCD 0 (hash_fwd_runs.h: block_to_level_chunk_paired).
 //  * no extract_position / transpose kernels: positions are read strided from the caller's buffer and features are written
 //    either as the [n,32] rows HashEncoder returns or as a level-major [16][n] stream of pairs that the fused MLP consumes with
 //    fully coalesced 256-B wave accesses (no 4-byte-per-64-byte-line partial writes from sixteen different XCDs).
@@ -32,6 +33,7 @@
 #include "hash_bwd_common.h"
 #include "hash_bwd_percorner.h"
 #include "hash_bwd_regions.h"
+#include "hash_fwd_runs.h"
 
 template <typename T, int LAYOUT>
 __device__ __forceinline__ void hash_fwd_body(uint32_t n, const float *__restrict__ pos, uint32_t stride, const T *__restrict__ table, const LevelTable &lt,
@@ -128,11 +130,18 @@ __device__ __forceinline__ void hash_fwd_body(uint32_t n, const float *__restric
 // adjacent lanes loading one each in the SAME instruction are merged by the address coalescer with no branch at all: 6 lines per (sample, hashed level) on average instead
 // of 8.  Bit-exact: the lanes swap halves (lane 2p ends up with every corner's first component, lane 2p + 1 with the second) and each sums its component's eight terms in the
 // reference's order, k = x + 2 y + 4 z.
-template <typename T, int LAYOUT>
+// (r10) MAP, the workgroup's (level, chunk): X2_MAP_LEVELS = block_to_level_chunk (XCD x: level 15 - x, then level x; rounds 6-9), X2_MAP_PAIRED = block_to_level_chunk_paired
+// (two XCDs share four levels), X2_MAP_SEL = the levels of `sel` alone, dealt out by sel_block - the levels k_hash_fwd_runs does not take (both hash_fwd_runs.h).  `sel` is
+// read by X2_MAP_SEL only.  Speed only: every (sample, level) is computed by one lane pair, the same way, under every map.
+enum { X2_MAP_LEVELS = 0, X2_MAP_PAIRED = 1, X2_MAP_SEL = 2 };
+template <typename T, int LAYOUT, int MAP = X2_MAP_LEVELS>
 __global__ __launch_bounds__(256) void k_hash_fwd_x2(uint32_t n, const float *__restrict__ pos, uint32_t stride, const T *__restrict__ table, LevelTable lt,
-                                                     T *__restrict__ out, uint32_t nblk, const uint32_t *__restrict__ n_valid) {
+                                                     T *__restrict__ out, uint32_t nblk, const uint32_t *__restrict__ n_valid, FwdSel sel) {
 	using P = typename Pair<T>::type;
-	uint32_t level, chunk; block_to_level_chunk(nblk, level, chunk);
+	uint32_t level, chunk;
+	if constexpr (MAP == X2_MAP_SEL) { if (!sel_block(sel, nblk, level, chunk)) return; }
+	else if constexpr (MAP == X2_MAP_PAIRED) { if (!block_to_level_chunk_paired(nblk, level, chunk)) return; }
+	else block_to_level_chunk(nblk, level, chunk);
 	uint32_t lim = n; if (n_valid) { uint32_t nv = *n_valid; lim = nv < n ? nv : n; }
 	const uint32_t off = lt.v[4 * level], size = lt.v[4 * level + 1], res = lt.v[4 * level + 2];
 	const float scale = __uint_as_float(lt.v[4 * level + 3]);
@@ -192,6 +201,7 @@ __global__ __launch_bounds__(256) void k_hash_bwd(uint32_t n, const float *__res
 	}
 }
 
+static bool level_run(const LevelTable &lt, int l);
 NGP_API int ngp_hash_encode_fwd(void *stream, uint32_t n, const float *pos, uint32_t pos_stride, const void *table, const uint32_t *level_table_host,
                                 void *out, int dtype, int out_layout, const uint32_t *n_valid) {
 	NGP_REQUIRE(n == 0 || (pos && table && level_table_host && out), NGP_E_ARG, "ngp_hash_encode_fwd: null pointer");
@@ -203,9 +213,46 @@ NGP_API int ngp_hash_encode_fwd(void *stream, uint32_t n, const float *pos, uint
 	hipStream_t s = (hipStream_t)stream;
 	// A/B hook NGP_HASH_FWD_X2: bit 0 = two lanes per (sample, level) for the fp32 table (default on), bit 1 = for the fp16 table (default off: its 8-byte pair loads stay)
 	static const int x2 = [] { const char *e = getenv("NGP_HASH_FWD_X2"); return e ? atoi(e) : 1; }();
+	// A/B hook NGP_HASH_FWD_MAP (r10): 1 (default) = fp32 table, k_hash_fwd_x2's workgroups by block_to_level_chunk_paired (two XCDs share four levels: the training launch
+	// 60.6 -> 50.6 us alone on the GPU); 0 = by block_to_level_chunk, the launch of rounds 6-9
+	static const int paired = [] { const char *e = getenv("NGP_HASH_FWD_MAP"); return e ? atoi(e) : 1; }();
+	// A/B hook NGP_HASH_FWD_RUNS (r10): 1 = fp32 table, the run levels (level_run: the levels the backward run-combines) through k_hash_fwd_runs and the others through
+	// k_hash_fwd_x2 - two launches, every XCD an equal share of each; 0 (default: the run kernel lost its A/B, 75 against 61 us, hash_fwd_runs.h) = one k_hash_fwd_x2 launch
+	// (read per call, like NGP_HASH_BWD_RUNS: tests/test_hash_fwd_runs.py runs both routings in one process)
+	const char *runs_env = getenv("NGP_HASH_FWD_RUNS");
+	const int runs = runs_env ? atoi(runs_env) : 0;
+	const FwdSel no_sel{};
+	if (dtype == NGP_F32 && (x2 & 1) && runs) {
+		FwdSel sel_run{}, sel_fine{};
+		for (int l = 0; l < 16; ++l) { FwdSel &t = level_run(lt, l) ? sel_run : sel_fine; t.level[t.m++] = (uint32_t)l; }
+		if (sel_run.m) {
+			if (sel_fine.m) {
+				const uint32_t nblk2 = min(div_up(n, 128), 4096u);
+#define GO2S(L) NGP_LAUNCH((k_hash_fwd_x2<float, L, X2_MAP_SEL>), dim3(8 * div_up(sel_fine.m * nblk2, 8)), block, 0, s, n, pos, pos_stride, (const float *)table, lt, (float *)out, nblk2, n_valid, sel_fine)
+				if (out_layout == NGP_LAYOUT_SOA) GO2S(NGP_LAYOUT_SOA); else GO2S(NGP_LAYOUT_AOS);
+#undef GO2S
+			}
+			const uint32_t nblkr = min(div_up(n, FWD_RUN_SPAN), 2048u);
+			// 16-byte accesses only where they are aligned: positions as 96-byte blocks (stride 3), a window's SOA feature pairs as 64 (level * n + first even)
+			const uint32_t wide = ((pos_stride == 3 && ((uintptr_t)pos & 15u) == 0) ? 1u : 0u) | ((out_layout == NGP_LAYOUT_SOA && (n & 1u) == 0 && ((uintptr_t)out & 15u) == 0) ? 2u : 0u);
+#define GOR(L) NGP_LAUNCH((k_hash_fwd_runs<float, L>), dim3(8 * div_up(sel_run.m * nblkr, 8)), dim3(FWD_RUN_WG), 0, s, n, pos, pos_stride, (const float *)table, lt, (float *)out, nblkr, n_valid, sel_run, wide)
+			if (out_layout == NGP_LAYOUT_SOA) GOR(NGP_LAYOUT_SOA); else GOR(NGP_LAYOUT_AOS);
+#undef GOR
+			NGP_LAUNCH_CHECK("ngp_hash_encode_fwd");
+			return 0;
+		}
+	}
+	if (dtype == NGP_F32 && (x2 & 1) && paired) {                                     // two lanes per (sample, level), the XCDs in pairs
+		const uint32_t nblk2 = min(div_up(n, 128), 4096u);
+#define GO2P(L) NGP_LAUNCH((k_hash_fwd_x2<float, L, X2_MAP_PAIRED>), dim3(32 * div_up(nblk2, 2)), block, 0, s, n, pos, pos_stride, (const float *)table, lt, (float *)out, nblk2, n_valid, no_sel)
+		if (out_layout == NGP_LAYOUT_SOA) GO2P(NGP_LAYOUT_SOA); else GO2P(NGP_LAYOUT_AOS);
+#undef GO2P
+		NGP_LAUNCH_CHECK("ngp_hash_encode_fwd");
+		return 0;
+	}
 	if ((dtype == NGP_F32 && (x2 & 1)) || (dtype == NGP_F16 && (x2 & 2))) {            // two lanes per (sample, level): 128 samples per workgroup
 		const uint32_t nblk2 = min(div_up(n, 128), 4096u);
-#define GO2(T, L) NGP_LAUNCH((k_hash_fwd_x2<T, L>), dim3(16 * nblk2), block, 0, s, n, pos, pos_stride, (const T *)table, lt, (T *)out, nblk2, n_valid)
+#define GO2(T, L) NGP_LAUNCH((k_hash_fwd_x2<T, L>), dim3(16 * nblk2), block, 0, s, n, pos, pos_stride, (const T *)table, lt, (T *)out, nblk2, n_valid, no_sel)
 		if (dtype == NGP_F32) { if (out_layout == NGP_LAYOUT_SOA) GO2(float, NGP_LAYOUT_SOA); else GO2(float, NGP_LAYOUT_AOS); }
 		else { if (out_layout == NGP_LAYOUT_SOA) GO2(__half, NGP_LAYOUT_SOA); else GO2(__half, NGP_LAYOUT_AOS); }
 #undef GO2
