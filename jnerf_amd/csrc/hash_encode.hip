@@ -134,6 +134,99 @@ __device__ __forceinline__ void hash_fwd_body(uint32_t n, const float *__restric
 // (two XCDs share four levels), X2_MAP_SEL = the levels of `sel` alone, dealt out by sel_block - the levels k_hash_fwd_runs does not take (both hash_fwd_runs.h).  `sel` is
 // read by X2_MAP_SEL only.  Speed only: every (sample, level) is computed by one lane pair, the same way, under every map.
 enum { X2_MAP_LEVELS = 0, X2_MAP_PAIRED = 1, X2_MAP_SEL = 2 };
+// (r11) The KIND of a level - how a lattice point becomes a table entry - is the same for every sample of a workgroup, so it is decided once, outside the sample loop, and
+// each kind has its own loop body: X2_DENSE = x + y res + z res^2 with grid_index's wrap of the +1 boundary corner (for a dense level whose size is a power of two the wrap
+// is grid_index's mask: both are index % size), X2_HASH_POW2 = the XOR hash masked (every hashed level GridEncode builds: 2^19 entries), X2_GENERAL = grid_index as it is
+// (a hashed level of any other size).  Same entries in every case; the additions below are grid_index's multiplications taken apart, in arithmetic modulo 2^32.
+enum { X2_DENSE = 0, X2_HASH_POW2 = 1, X2_GENERAL = 2 };
+#define X2_SIZE_MAX32 (1u << 28)      // the specialised bodies address an entry by a 32-bit byte offset (8 bytes per fp32 entry); a larger level is X2_GENERAL's
+#ifndef NGP_HASH_FWD_DEPTH
+#define NGP_HASH_FWD_DEPTH 2          // samples whose loads are in flight together per lane pair (measured 1 | 2 | 4: profiles/r11_hash_fwd_trips.md)
+#endif
+// the four entries of one x face of the cell: j = (y corner, z corner)
+template <int KIND>
+__device__ __forceinline__ void x2_face_entries(uint32_t size, uint32_t res, bool dense, uint32_t gx, uint32_t gy, uint32_t gz, uint32_t (&e)[4]) {
+	if constexpr (KIND == X2_DENSE) {
+		const uint32_t rr = res * res, b = gx + gy * res + gz * rr;
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) e[j] = b + ((j & 1u) ? res : 0u) + ((j >> 1) ? rr : 0u);
+		// grid_index's wrap: taken by the +1 boundary corner only, the division never for in-range positions - one test for the four entries, the wrap itself per entry as there
+		if (max(max(e[0], e[1]), max(e[2], e[3])) >= size) {
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) if (e[j] >= size) { e[j] -= size; if (e[j] >= size) e[j] %= size; }
+		}
+	} else if constexpr (KIND == X2_HASH_POW2) {
+		const uint32_t hy = gy * 19349663u, hz = gz * 83492791u, mask = size - 1u;
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) e[j] = (gx ^ (hy + ((j & 1u) ? 19349663u : 0u)) ^ (hz + ((j >> 1) ? 83492791u : 0u))) & mask;
+	} else {
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) e[j] = grid_index(size, res, dense, gx, gy + (j & 1u), gz + (j >> 1));
+	}
+}
+// One trip of a lane pair: samples i, i + step, ... (NS of them, all below the count).  All NS samples' position loads are issued together, then all 4 NS gathers, then the
+// arithmetic - one memory round trip for the positions and one for the table per trip instead of per sample.
+template <typename T, int LAYOUT, int KIND, int NS>
+__device__ __forceinline__ void x2_trip(uint32_t n, const float *__restrict__ pos, uint32_t stride, const typename Pair<T>::type *__restrict__ tab, uint32_t size, uint32_t res,
+                                        bool dense, float scale, T *__restrict__ out, uint32_t level, uint32_t xc, uint32_t i, uint32_t step) {
+	using P = typename Pair<T>::type;
+	Corner c[NS];
+#pragma unroll
+	for (int s = 0; s < NS; ++s) c[s] = locate(pos, stride, i + (uint32_t)s * step, scale);
+	P v[NS][4];
+#pragma unroll
+	for (int s = 0; s < NS; ++s) {
+		uint32_t e[4];
+		x2_face_entries<KIND>(size, res, dense, c[s].g[0] + xc, c[s].g[1], c[s].g[2], e);
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) {                                                 // every gather of the trip is issued before the first use
+			if constexpr (KIND == X2_GENERAL) v[s][j] = tab[e[j]];
+			else v[s][j] = *reinterpret_cast<const P *>(reinterpret_cast<const char *>(tab) + e[j] * (uint32_t)sizeof(P));   // a 32-bit byte offset (size <= X2_SIZE_MAX32): no 64-bit address arithmetic per gather
+		}
+	}
+#pragma unroll
+	for (int s = 0; s < NS; ++s) {
+		float acc = 0.f;
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) {
+			const float wy = (j & 1u) ? c[s].w[1] : 1 - c[s].w[1], wz = (j >> 1) ? c[s].w[2] : 1 - c[s].w[2];
+			const float w0 = ((1 - c[s].w[0]) * wy) * wz, w1 = (c[s].w[0] * wy) * wz;    // the reference's x, y, z multiplication order
+			const float2 f = to_f2(v[s][j]);
+			const float own = xc ? f.y : f.x, give = xc ? f.x : f.y;
+			// the partner's value of MY component: quad_perm [1, 0, 3, 2] on the vector pipe (rounds 6-10: __shfl_xor, a bpermute through the LDS pipe and its address register)
+			const float got = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(give), 0xB1, 0xf, 0xf, true));
+			acc += w0 * (xc ? got : own);                                                // corner k = 2 j     (x = g)
+			acc += w1 * (xc ? own : got);                                                // corner k = 2 j + 1 (x = g + 1)
+		}
+		const uint32_t is = i + (uint32_t)s * step;
+		const size_t o = (LAYOUT == NGP_LAYOUT_SOA ? (size_t)level * n + is : (size_t)is * 16 + level) * 2u + xc;
+		if (sizeof(T) == 4) reinterpret_cast<float *>(out)[o] = acc;
+		else reinterpret_cast<__half *>(out)[o] = __float2half_rn(acc);
+	}
+}
+// The sample loop of one level kind: the lane pair takes samples first, first + step, ... below lim, NGP_HASH_FWD_DEPTH per trip while that many are left and one per trip
+// after that.  Both lanes of a pair hold the same sample numbers, so they take the same trips of the same depth and the swap in x2_trip always has its partner - also in
+// the wavefront that straddles lim, where the pairs disagree.  `left` counts down instead of the sample number counting up: no sum here can pass 2^32.
+template <typename T, int LAYOUT, int KIND>
+__device__ __forceinline__ void x2_samples(uint32_t n, uint32_t lim, const float *__restrict__ pos, uint32_t stride, const typename Pair<T>::type *__restrict__ tab, uint32_t size,
+                                           uint32_t res, bool dense, float scale, T *__restrict__ out, uint32_t level, uint32_t first, uint32_t step) {
+	constexpr uint32_t NS = NGP_HASH_FWD_DEPTH;
+	const uint32_t xc = threadIdx.x & 1u;
+	if (first >= lim) return;
+	uint32_t i = first, left = lim - first;                                           // samples i, i + step, ... exist while k step < left
+	if constexpr (NS > 1) {
+		while (left > (NS - 1u) * step) {
+			x2_trip<T, LAYOUT, KIND, (int)NS>(n, pos, stride, tab, size, res, dense, scale, out, level, xc, i, step);
+			if (left <= NS * step) return;
+			i += NS * step; left -= NS * step;
+		}
+	}
+	for (;;) {
+		x2_trip<T, LAYOUT, KIND, 1>(n, pos, stride, tab, size, res, dense, scale, out, level, xc, i, step);
+		if (left <= step) return;
+		i += step; left -= step;
+	}
+}
 template <typename T, int LAYOUT, int MAP = X2_MAP_LEVELS>
 __global__ __launch_bounds__(256) void k_hash_fwd_x2(uint32_t n, const float *__restrict__ pos, uint32_t stride, const T *__restrict__ table, LevelTable lt,
                                                      T *__restrict__ out, uint32_t nblk, const uint32_t *__restrict__ n_valid, FwdSel sel) {
@@ -147,29 +240,11 @@ __global__ __launch_bounds__(256) void k_hash_fwd_x2(uint32_t n, const float *__
 	const float scale = __uint_as_float(lt.v[4 * level + 3]);
 	const bool dense = level_is_dense(size, res);
 	const P *tab = reinterpret_cast<const P *>(table) + off;
-	const uint32_t xc = threadIdx.x & 1u;
-	// (both lanes of a pair take the same trips, so the swap below always has its partner)
-	for (uint32_t i = chunk * 128u + (threadIdx.x >> 1); i < lim; i += nblk * 128u) {
-		const Corner c = locate(pos, stride, i, scale);
-		const uint32_t gx = c.g[0] + xc;
-		P v[4];
-#pragma unroll
-		for (uint32_t j = 0; j < 4; ++j) v[j] = tab[grid_index(size, res, dense, gx, c.g[1] + (j & 1u), c.g[2] + (j >> 1))];      // j = (y corner, z corner); all four gathers issued before the first use
-		float acc = 0.f;
-#pragma unroll
-		for (uint32_t j = 0; j < 4; ++j) {
-			const float wy = (j & 1u) ? c.w[1] : 1 - c.w[1], wz = (j >> 1) ? c.w[2] : 1 - c.w[2];
-			const float w0 = ((1 - c.w[0]) * wy) * wz, w1 = (c.w[0] * wy) * wz;          // the reference's x, y, z multiplication order
-			const float2 f = to_f2(v[j]);
-			const float own = xc ? f.y : f.x, give = xc ? f.x : f.y;
-			const float got = __shfl_xor(give, 1);                                      // the partner's value of MY component
-			acc += w0 * (xc ? got : own);                                                // corner k = 2 j     (x = g)
-			acc += w1 * (xc ? own : got);                                                // corner k = 2 j + 1 (x = g + 1)
-		}
-		const size_t o = (LAYOUT == NGP_LAYOUT_SOA ? (size_t)level * n + i : (size_t)i * 16 + level) * 2u + xc;
-		if (sizeof(T) == 4) reinterpret_cast<float *>(out)[o] = acc;
-		else reinterpret_cast<__half *>(out)[o] = __float2half_rn(acc);
-	}
+	const uint32_t first = chunk * 128u + (threadIdx.x >> 1), step = nblk * 128u;   // (nblk <= 2^16: the host)
+	const bool small = size <= X2_SIZE_MAX32;
+	if (small && dense) x2_samples<T, LAYOUT, X2_DENSE>(n, lim, pos, stride, tab, size, res, true, scale, out, level, first, step);
+	else if (small && (size & (size - 1u)) == 0u) x2_samples<T, LAYOUT, X2_HASH_POW2>(n, lim, pos, stride, tab, size, res, false, scale, out, level, first, step);
+	else x2_samples<T, LAYOUT, X2_GENERAL>(n, lim, pos, stride, tab, size, res, dense, scale, out, level, first, step);
 }
 
 template <typename T, typename G, int LAYOUT>
@@ -202,6 +277,25 @@ __global__ __launch_bounds__(256) void k_hash_bwd(uint32_t n, const float *__res
 }
 
 static bool level_run(const LevelTable &lt, int l);
+// (r11) Chunks of 128 samples in flight per level for k_hash_fwd_x2 (a workgroup takes chunks chunk, chunk + nblk, ... of its level).  Fewer chunks = longer workgroups: the
+// level row, the kind and the count are paid once for more samples and a trip holds NGP_HASH_FWD_DEPTH samples' loads - but a launch that no longer fills the machine
+// several times over ends on its slowest workgroups.  Paired map: by launch size, from the sweep in profiles/r11_hash_fwd_trips.md; the other maps keep rounds 6-10's.
+// A/B and test hook NGP_HASH_FWD_CHUNKS (read per call): forces the number for every map.
+#define X2_CHUNKS_MAX 65536u          // step = 128 nblk stays below 2^23 (x2_samples multiplies it by the depth)
+#define X2_CHUNKS_SMALL_N (1u << 19)  // launches up to this many samples (the 2^18-sample training batch: alone on the GPU 42.4 us at 512 chunks, 42.8 at 1024, 46.8 at 2048 = one trip
+                                      // each; in the step, beside the side stream, 2334 / 2337 it/s at 512, 2345 / 2349 at 1024, 2315 / 2327 at 2048) ...
+#ifndef X2_CHUNKS_SMALL
+#define X2_CHUNKS_SMALL 1024u         // ... keep this many chunks in flight,
+#endif
+#define X2_CHUNKS_LARGE 4096u         // larger ones (the 2^20-point refresh query, the 4 M-row inference buffers: 235 us at 4096 chunks, 242 at 1024, 254 at 512) this many
+static uint32_t x2_chunks(uint32_t n, bool paired) {
+	const uint32_t all = div_up(n, 128);
+	const char *e = getenv("NGP_HASH_FWD_CHUNKS");
+	const long forced = e ? atol(e) : 0;
+	if (forced > 0) return min((uint32_t)min(forced, (long)X2_CHUNKS_MAX), all);
+	if (!paired) return min(all, 4096u);
+	return min(all, n <= X2_CHUNKS_SMALL_N ? X2_CHUNKS_SMALL : X2_CHUNKS_LARGE);
+}
 NGP_API int ngp_hash_encode_fwd(void *stream, uint32_t n, const float *pos, uint32_t pos_stride, const void *table, const uint32_t *level_table_host,
                                 void *out, int dtype, int out_layout, const uint32_t *n_valid) {
 	NGP_REQUIRE(n == 0 || (pos && table && level_table_host && out), NGP_E_ARG, "ngp_hash_encode_fwd: null pointer");
@@ -215,7 +309,8 @@ NGP_API int ngp_hash_encode_fwd(void *stream, uint32_t n, const float *pos, uint
 	static const int x2 = [] { const char *e = getenv("NGP_HASH_FWD_X2"); return e ? atoi(e) : 1; }();
 	// A/B hook NGP_HASH_FWD_MAP (r10): 1 (default) = fp32 table, k_hash_fwd_x2's workgroups by block_to_level_chunk_paired (two XCDs share four levels: the training launch
 	// 60.6 -> 50.6 us alone on the GPU); 0 = by block_to_level_chunk, the launch of rounds 6-9
-	static const int paired = [] { const char *e = getenv("NGP_HASH_FWD_MAP"); return e ? atoi(e) : 1; }();
+	const char *map_env = getenv("NGP_HASH_FWD_MAP");                      // (r11: read per call, like NGP_HASH_FWD_RUNS below - tests/test_hash_fwd_trips.py runs both maps in one process)
+	const int paired = map_env ? atoi(map_env) : 1;
 	// A/B hook NGP_HASH_FWD_RUNS (r10): 1 = fp32 table, the run levels (level_run: the levels the backward run-combines) through k_hash_fwd_runs and the others through
 	// k_hash_fwd_x2 - two launches, every XCD an equal share of each; 0 (default: the run kernel lost its A/B, 75 against 61 us, hash_fwd_runs.h) = one k_hash_fwd_x2 launch
 	// (read per call, like NGP_HASH_BWD_RUNS: tests/test_hash_fwd_runs.py runs both routings in one process)
@@ -227,7 +322,7 @@ NGP_API int ngp_hash_encode_fwd(void *stream, uint32_t n, const float *pos, uint
 		for (int l = 0; l < 16; ++l) { FwdSel &t = level_run(lt, l) ? sel_run : sel_fine; t.level[t.m++] = (uint32_t)l; }
 		if (sel_run.m) {
 			if (sel_fine.m) {
-				const uint32_t nblk2 = min(div_up(n, 128), 4096u);
+				const uint32_t nblk2 = x2_chunks(n, false);
 #define GO2S(L) NGP_LAUNCH((k_hash_fwd_x2<float, L, X2_MAP_SEL>), dim3(8 * div_up(sel_fine.m * nblk2, 8)), block, 0, s, n, pos, pos_stride, (const float *)table, lt, (float *)out, nblk2, n_valid, sel_fine)
 				if (out_layout == NGP_LAYOUT_SOA) GO2S(NGP_LAYOUT_SOA); else GO2S(NGP_LAYOUT_AOS);
 #undef GO2S
@@ -243,7 +338,7 @@ NGP_API int ngp_hash_encode_fwd(void *stream, uint32_t n, const float *pos, uint
 		}
 	}
 	if (dtype == NGP_F32 && (x2 & 1) && paired) {                                     // two lanes per (sample, level), the XCDs in pairs
-		const uint32_t nblk2 = min(div_up(n, 128), 4096u);
+		const uint32_t nblk2 = x2_chunks(n, true);
 #define GO2P(L) NGP_LAUNCH((k_hash_fwd_x2<float, L, X2_MAP_PAIRED>), dim3(32 * div_up(nblk2, 2)), block, 0, s, n, pos, pos_stride, (const float *)table, lt, (float *)out, nblk2, n_valid, no_sel)
 		if (out_layout == NGP_LAYOUT_SOA) GO2P(NGP_LAYOUT_SOA); else GO2P(NGP_LAYOUT_AOS);
 #undef GO2P
@@ -251,7 +346,7 @@ NGP_API int ngp_hash_encode_fwd(void *stream, uint32_t n, const float *pos, uint
 		return 0;
 	}
 	if ((dtype == NGP_F32 && (x2 & 1)) || (dtype == NGP_F16 && (x2 & 2))) {            // two lanes per (sample, level): 128 samples per workgroup
-		const uint32_t nblk2 = min(div_up(n, 128), 4096u);
+		const uint32_t nblk2 = x2_chunks(n, false);
 #define GO2(T, L) NGP_LAUNCH((k_hash_fwd_x2<T, L>), dim3(16 * nblk2), block, 0, s, n, pos, pos_stride, (const T *)table, lt, (T *)out, nblk2, n_valid, no_sel)
 		if (dtype == NGP_F32) { if (out_layout == NGP_LAYOUT_SOA) GO2(float, NGP_LAYOUT_SOA); else GO2(float, NGP_LAYOUT_AOS); }
 		else { if (out_layout == NGP_LAYOUT_SOA) GO2(__half, NGP_LAYOUT_SOA); else GO2(__half, NGP_LAYOUT_AOS); }
